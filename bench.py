@@ -14,7 +14,13 @@ with t_step the max over ranks.  Beside it (strong_scaling): one global batch
 of 256 graphs split 256/N per rank, timed the same way; the per-step
 all-reduce's time and bus bandwidth and the min / max rank step time.
 
-Run:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+      A plain run sets up, runs W warm-up steps, times K steps, writes the
+      last timed step's outputs if --dump-outputs is given (dump_outputs) and
+      prints the result line (headline).  --full: every other leg after that
+      (event-instrumented pass with roofline and kernel breakdown, dropout on,
+      strong scaling, the all-reduce alone, the side measurements, the CPU
+      baseline), added to the same line.
       N > 1: one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set)
       the ranks are torchrun's and WORLD_SIZE must equal N; started plainly,
       bench.py starts the N ranks itself (spawn_ranks: N fresh child
@@ -817,11 +823,86 @@ def launch_rehearsal(args):
         tdist.destroy_process_group()
 
 
+DUMP_ARRAY_MAX_BYTES = 16 << 20     # per array; the 14 arrays of a dump then stay below 64 MB together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname, tensors, rank=0):
+    """--dump-outputs: write each tensor of `tensors` (name -> device tensor)
+    as dirname/<name>.npy in float32 (rank 0; rank r > 0 writes
+    dirname/rank<r>_<name>.npy).  An array above DUMP_ARRAY_MAX_BYTES is cut to
+    a fixed sample of its leading index (graphs of the batch): the sorted
+    choice of a generator seeded with DUMP_SAMPLE_SEED, the same in every run,
+    so two builds run with the same arguments write comparable files."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in tensors.items():
+        x = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        if x.nbytes > DUMP_ARRAY_MAX_BYTES:
+            keep = max(1, x.shape[0] * DUMP_ARRAY_MAX_BYTES // x.nbytes)
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(x.shape[0], keep, replace=False))
+            x = np.ascontiguousarray(x[rows])
+        np.save(os.path.join(dirname, ("rank%d_" % rank if rank else "") + name + ".npy"), x)
+
+
+def headline(args, world, dt, dt_min, grad_bytes):
+    """The result line of a plain run: the headline figure of the K timed
+    steps (dt: seconds per step, the slowest rank's; dt_min: the fastest's)
+    and what describes the run.  --full adds its legs to this dict."""
+    import torch.distributed as tdist
+    b, v, h, T = CFG["b"], CFG["v"], CFG["h"], CFG["T"]
+    fpg = flops_per_graph(v, h, 2 * CFG["e"], T)["total"]
+    return {
+        "metric": "instances/sec (graphs/s) GGNN fwd+bwd, hidden=256 v=128 e=4 T=5",
+        "value": world * b / dt,
+        "unit": "graphs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"fp32": "fp32", "fp16": "fp16", "bf16": "bf16"}[args.precision],
+        "precision_note": {"fp32": "fp32-class: every non-exact MFMA operand of the forward and of the "
+                                   "dh/dX chain as an f16 hi/lo limb pair (3 products), fp32 accumulation, "
+                                   "except k_gru_bwd's Wc^T / Wg^T (the hi limb only: dz hi/lo x W hi, 2 "
+                                   "products) and k_prop_bwd's dM W_c^T (hi x hi on f16 MFMAs, both limb "
+                                   "corrections on the block-scaled fp8 MFMA: e5m2 dM, e4m3 W_c^T); the "
+                                   "weight-gradient GEMMs (k_wgrad256) take SINGLE f16 "
+                                   "operands, on a power-of-two-scaled gradient; parity <= 1e-3 vs the fp32 "
+                                   "reference (tests/test_gpu_parity.py, incl. loss-scale gradients; the "
+                                   "backward's limb policy: tests/test_precision_policies.py)",
+                           "fp16": "f16 MFMA operands, fp32 accumulation (reduced precision)",
+                           "bf16": "bf16 MFMA operands, fp32 accumulation (reduced precision)"}[args.precision],
+        "data": "synthetic (SURVEY §8d generator: Bernoulli(0.1) adjacency on n~U{v/2..v} active nodes, glorot weights)",
+        "config": {"workload": "configs[2]: b=256 graphs/GPU, v=128, hidden=256, e=4 (C=8), T=5, fwd+bwd",
+                   "global_batch": world * b, "parallelism": "dp%d" % world},
+        "full": bool(args.full),
+        "achieved_step_tflops": world * b * fpg / dt / 1e12,
+        "rank_step_ms": {"max": dt * 1e3, "min": dt_min * 1e3,
+                         "note": "each rank's K-step average; value uses the max (the slowest rank)"},
+        "all_reduce": {"backend": tdist.get_backend() if tdist.is_initialized() else None,
+                       "bytes_per_step": grad_bytes},
+        "launcher": os.environ.get("GGNN_BENCH_LAUNCHER", "external (torch.distributed.run)"
+                                   if "WORLD_SIZE" in os.environ else "single process"),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures: the event-instrumented "
+                         "pass (roofline, kernel breakdown), the dropout-on leg, the strong-scaling leg and the "
+                         "all-reduce's cost, the side measurements (other precisions, real-density graphs, "
+                         "run_epoch) and the CPU baseline.  The options below that switch those legs off or on "
+                         "apply with --full only; without it the run is set-up, warm-up, the timed steps and "
+                         "the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (h_T, dL/dh0, the weight "
+                         "gradients, the updated weights) as DIR/<name>.npy, float32 (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dropout-keep", type=float, default=0.9,
                     help="keep probability of the dropout-on line (graph_state_dropout_keep_prob)")
@@ -850,6 +931,8 @@ def main():
     ap.add_argument("--spawn-timeout", type=float, default=None,
                     help="seconds after which the self-started ranks are stopped (N > 1 without torchrun)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -937,6 +1020,20 @@ def main():
     barrier()
     # timed region: exactly K steps, nothing else on the stream
     dt = timed(step, args.steps)
+    if args.dump_outputs:
+        # the state the last timed step left, before any later leg steps again
+        last = {"hT": out, "dh0": gviews["h0"]}
+        last.update(("grad_" + k, grads.views[k]) for k in GRAD_ORDER)
+        last.update(("weight_" + k, w_d[k]) for k in sorted(w_d))
+        dump_outputs(args.dump_outputs, last, rank)
+    if not args.full:
+        # a plain run ends here: the headline figure needs nothing below
+        (dt,), (dt_min,) = rank_spread([dt], dev)
+        if rank == 0:
+            print(json.dumps(headline(args, world, dt, dt_min, grads.nbytes)), flush=True)
+        if tdist.is_initialized():
+            tdist.destroy_process_group()
+        return
     # the same K steps again with a HIP event pair around every library launch
     # (kernel durations for the roofline; the events add gaps between launches,
     # so this pass is not the headline time) and around the all-reduce
@@ -1071,39 +1168,10 @@ def main():
                if rank == 0 and world == 1 and not args.no_side else None)
 
     if rank == 0:
-        fpg = flops_per_graph(v, h, C, T)["total"]
-        value = world * b / dt
-        res = {
-            "metric": "instances/sec (graphs/s) GGNN fwd+bwd, hidden=256 v=128 e=4 T=5",
-            "value": value,
-            "unit": "graphs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"fp32": "fp32", "fp16": "fp16", "bf16": "bf16"}[args.precision],
-            "precision_note": {"fp32": "fp32-class: every non-exact MFMA operand of the forward and of the "
-                                       "dh/dX chain as an f16 hi/lo limb pair (3 products), fp32 accumulation, "
-                                       "except k_gru_bwd's Wc^T / Wg^T (the hi limb only: dz hi/lo x W hi, 2 "
-                                       "products) and k_prop_bwd's dM W_c^T (hi x hi on f16 MFMAs, both limb "
-                                       "corrections on the block-scaled fp8 MFMA: e5m2 dM, e4m3 W_c^T); the "
-                                       "weight-gradient GEMMs (k_wgrad256) take SINGLE f16 "
-                                       "operands, on a power-of-two-scaled gradient; parity <= 1e-3 vs the fp32 "
-                                       "reference (tests/test_gpu_parity.py, incl. loss-scale gradients; the "
-                                       "backward's limb policy: tests/test_precision_policies.py)",
-                               "fp16": "f16 MFMA operands, fp32 accumulation (reduced precision)",
-                               "bf16": "bf16 MFMA operands, fp32 accumulation (reduced precision)"}[args.precision],
-            "data": "synthetic (SURVEY §8d generator: Bernoulli(0.1) adjacency on n~U{v/2..v} active nodes, glorot weights)",
-            "config": {"workload": "configs[2]: b=256 graphs/GPU, v=128, hidden=256, e=4 (C=8), T=5, fwd+bwd",
-                       "global_batch": world * b, "parallelism": "dp%d" % world},
+        res = headline(args, world, dt, dt_min, grads.nbytes)
+        res.update({
             "roofline": roof,
-            "achieved_step_tflops": world * b * fpg / dt / 1e12,
             "kernel_breakdown": breakdown,
-            "rank_step_ms": {"max": dt * 1e3, "min": dt_min * 1e3,
-                             "note": "each rank's K-step average; value uses the max (the slowest rank)"},
             "strong_scaling": {"value": b / dt_strong, "unit": "graphs/s", "ms_per_step": dt_strong * 1e3,
                                "ms_per_step_min_rank": dt_strong_min * 1e3, "per_rank_batch": bs,
                                "global_batch": b, "scaling": "strong",
@@ -1121,8 +1189,6 @@ def main():
                                    "stream around the collective in the instrumented pass (includes waiting for "
                                    "the slowest rank); isolated_ms_per_call: back-to-back all-reduces after a "
                                    "barrier; bus bandwidth 2(N-1)/N S / t"}),
-            "launcher": os.environ.get("GGNN_BENCH_LAUNCHER", "external (torch.distributed.run)"
-                                       if "WORLD_SIZE" in os.environ else "single process"),
             "ms_per_step_event_instrumented": dt_instr * 1e3,
             "adjacency_feed": feed_cmp,
             "dropout_on": None if args.no_dropout_leg else {
@@ -1140,7 +1206,7 @@ def main():
             "real_density_c92": real,
             "strong_split_one_gpu": strong1,
             "end_to_end_run_epoch": e2e,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.cpu_reps)
         print(json.dumps(res), flush=True)

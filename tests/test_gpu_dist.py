@@ -147,7 +147,7 @@ def test_bench_two_ranks_run_epoch_rehearsal():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--e2e-only", "--dist-backend", "gloo"]
+           "--warmup", "1", "--full", "--e2e-only", "--dist-backend", "gloo"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -163,7 +163,7 @@ def test_bench_two_ranks_rehearsal():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--no-side", "--dist-backend", "gloo"]
+           "--warmup", "1", "--full", "--no-side", "--dist-backend", "gloo"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -179,7 +179,7 @@ def test_bench_self_started_two_ranks():
     processes, before any GPU call in the parent), here as two gloo ranks on
     the one GPU, and relays rank 0's one JSON line with n_gpus = 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-side",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-side",
            "--dist-backend", "gloo", "--spawn-timeout", "240"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -278,7 +278,7 @@ def test_bench_one_rank_rccl_rehearsal():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "1", "--steps", "3",
-           "--warmup", "1", "--no-side", "--no-cpu-baseline", "--dist-backend", "nccl"]
+           "--warmup", "1", "--full", "--no-side", "--no-cpu-baseline", "--dist-backend", "nccl"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,4 +1,4 @@
-"""Print the headline numbers of bench.py JSON logs: python tools/bench_summary.py log..."""
+"""Print the headline numbers of `bench.py --full` JSON logs: python tools/bench_summary.py log..."""
 import json
 import sys
 

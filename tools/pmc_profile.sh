@@ -2,8 +2,8 @@
 # PMC passes over a short bench run (one counter group per pass, no tracing
 # domains mixed in).  Usage (GPU box): bash tools/pmc_profile.sh OUTDIR [bench args]
 set -e
-OUT=${1:-gpurun_out/pmc}; shift || true
-ARGS=${@:---steps 2 --warmup 1 --no-cpu-baseline --no-side}
+OUT=${1:-profile_out/pmc}; shift || true
+ARGS=${@:---steps 2 --warmup 1 --full --no-cpu-baseline --no-side}
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 i=0
