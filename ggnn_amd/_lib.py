@@ -31,8 +31,9 @@ EXPORTED = (
     "ggnn_profile_end", "ggnn_embed_forward", "ggnn_embed_backward", "ggnn_embed_workspace_bytes",
     "ggnn_embed_backward_ws", "ggnn_embed_lookup_rows", "ggnn_heads_workspace_bytes",
     "ggnn_heads_forward", "ggnn_heads_backward", "ggnn_dbg_gemm", "ggnn_dbg_gemm_ex",
-    "ggnn_adam_step_dev", "ggnn_heads_forward_dev", "ggnn_heads_backward_dev",
+    "ggnn_adam_step_dev", "ggnn_heads_forward_dev", "ggnn_heads_backward_dev", "ggnn_heads_decode",
 )
+DECODE_COUNTS = 5   # include/ggnn.h GGNN_DECODE_COUNTS: n_kept, las, uas, lab, regular
 NUM_KERNEL_KINDS = 11
 
 
@@ -125,6 +126,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
         lib.ggnn_heads_forward_dev.argtypes = [_DP, _P, _I, _P, _P, F, U64, _P, _P, _P, _P]
         lib.ggnn_heads_backward_dev.restype = _I
         lib.ggnn_heads_backward_dev.argtypes = [_DP, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]
+        lib.ggnn_heads_decode.restype = _I
+        lib.ggnn_heads_decode.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P]
         lib.ggnn_dbg_gemm.restype = _I
         lib.ggnn_dbg_gemm.argtypes = [_DP, _I, _I, _I, _P, _P, _P, _P]
         lib.ggnn_dbg_gemm_ex.restype = _I

@@ -20,6 +20,7 @@
 #include "k_optim.h"
 #include "k_wgrad.h"
 #include "k_head.h"
+#include "k_decode.h"
 #include "k_gemm.h"
 #include "k_gemm_ring.h"
 #include "k_generic.h"
@@ -1722,6 +1723,36 @@ int ggnn_heads_backward_dev(const ggnn_dims* d, const ggnn_output_head* heads, i
                             float* dh0, ggnn_stream_t stream) {
   if (!target_num) return fail(GGNN_EINVAL, "heads_backward_dev: NULL target_num");
   return heads_backward_impl(d, heads, nheads, hT, h0, 0.f, target_num, d_loss, ws, dhT, dh0, stream);
+}
+
+// the heads' probabilities -> predicted (head, label) per node and the LAS /
+// UAS counts per graph (k_decode.h); booked under the heads kind
+static_assert(GGNN_DECODE_COUNTS == DECODE_COUNTS, "counts layout");
+int ggnn_heads_decode(const ggnn_dims* d, const float* probs_head, int32_t o, const float* probs_label, int32_t oe,
+                      const float* gold_head, const float* gold_label, const int32_t* n_nodes, int32_t* pred,
+                      int32_t* gold, int32_t* counts, ggnn_stream_t stream) {
+  if (!d) return fail(GGNN_EINVAL, "heads_decode: dims is NULL");
+  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "heads_decode: b, v must be >= 1");
+  if (o < 1 || o > HEAD_MAXO || oe < 1 || oe > HEAD_MAXO)
+    return fail(GGNN_EINVAL, "heads_decode: o and oe must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
+                                 std::to_string(o) + ", " + std::to_string(oe) + ")");
+  if (d->v > o)
+    return fail(GGNN_EINVAL, "heads_decode: v " + std::to_string(d->v) + " > o " + std::to_string(o));
+  if (!probs_head || !probs_label || !n_nodes || !pred || !counts)
+    return fail(GGNN_EINVAL, "heads_decode: NULL pointer");
+  if ((gold_head == nullptr) != (gold_label == nullptr))
+    return fail(GGNN_EINVAL, "heads_decode: gold_head and gold_label must be given together (one is NULL)");
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+#define HDEC(NI_)                                                                                                  \
+  hipLaunchKernelGGL(k_heads_decode<NI_>, dim3((unsigned)d->b), dim3(256), 0, s, probs_head, (int)o, probs_label,  \
+                     (int)oe, gold_head, gold_label, (const int*)n_nodes, (int)d->v, (int*)pred,                   \
+                     gold_head ? (int*)gold : nullptr, (int*)counts)
+  if (std::max(o, oe) <= 256) HDEC(4);
+  else HDEC(HEAD_MAXO / 64);
+#undef HDEC
+  LAUNCHCHK();
+  return GGNN_OK;
 }
 
 }  // extern "C"

@@ -136,6 +136,125 @@ def batch_las_uas(labels, computed_values, num_vertices, mask, labels_e, compute
     return acc_las / b, acc_uas / b, acc_uas_e / b
 
 
+def closed_form_masks(n_nodes, num_vertices, output_size, output_size_edges):
+    """The btb masks of ``get_mask`` for a batch: (node_mask [b, v, o] with 1
+    where i < n and j < n, node_mask_edges [b, v, e] with 1 where i < n), bool."""
+    n = np.asarray(n_nodes).reshape(-1, 1)
+    r = np.arange(int(num_vertices))[None, :] < n
+    c = np.arange(int(output_size))[None, :] < n
+    return r[:, :, None] & c[:, None, :], np.broadcast_to(r[:, :, None], r.shape + (int(output_size_edges),))
+
+
+def decode_arrays(probs, probs_e, n_nodes, labels=None, labels_e=None):
+    """The host form of ``ggnn_heads_decode`` (include/ggnn.h), written with
+    the scorer's own ``_first_max``: probs [b, v, o] and probs_e [b, v, e] are
+    masked in ``get_mask``'s closed form for n_nodes [b] (as
+    results_reshaped_btb masks them), every node row 1..v-1 takes its first
+    maximum (adj_mat_to_target), labels / labels_e (0/1, same shapes) their
+    first exact 1.  Returns (pred [b, v, 2], gold [b, v, 2] or None, counts
+    [b, 5]) as int32: zero-based (head, label) columns, -1 = the node is
+    skipped; counts = (n_kept, las, uas, lab, regular) per graph, where
+    regular says that every list skips the same nodes and the rows i < n hold
+    no NaN / inf -- then the first four are batch_las_uas's per-graph counts."""
+    p, pe = np.asarray(probs, np.float32), np.asarray(probs_e, np.float32)
+    if p.ndim != 3 or pe.ndim != 3 or p.shape[:2] != pe.shape[:2]:
+        raise ValueError("probs [b, v, o] and probs_e [b, v, e] expected, got %s and %s" % (p.shape, pe.shape))
+    b, v, o = p.shape
+    e = pe.shape[2]
+    n = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
+    if n.shape[0] != b:
+        raise ValueError("n_nodes: %d values for %d graphs" % (n.shape[0], b))
+    m, m_e = closed_form_masks(n, v, o, e)
+    with np.errstate(invalid="ignore"):     # (inf * 0: a NaN, as on the reference's path)
+        res, res_e = p * m.astype(np.float32), pe * m_e.astype(np.float32)
+    pred = np.full((b, v, 2), -1, np.int32)
+    keep, first = _first_max(res[:, 1:, :], True)
+    pred[:, 1:, 0] = np.where(keep, first, -1)
+    keep, first = _first_max(res_e[:, 1:, :], True)
+    pred[:, 1:, 1] = np.where(keep, first, -1)
+    real = m_e[:, 1:, 0]
+    bad = ((~np.isfinite(p[:, 1:, :])).any(axis=2) | (~np.isfinite(pe[:, 1:, :])).any(axis=2)) & real
+    kept = pred[:, 1:, 0] >= 0
+    regular = ((pred[:, 1:, 1] >= 0) == kept).all(axis=1) & ~bad.any(axis=1)
+    counts = np.zeros((b, 5), np.int32)
+    gold = None
+    if (labels is None) != (labels_e is None):
+        raise ValueError("labels and labels_e are given together")
+    if labels is not None:
+        y, ye = np.asarray(labels, np.float32), np.asarray(labels_e, np.float32)
+        if y.shape != p.shape or ye.shape != pe.shape:
+            raise ValueError("labels must have the probabilities' shapes")
+        gold = np.full((b, v, 2), -1, np.int32)
+        keep, first = _first_max(y[:, 1:, :], False)
+        gold[:, 1:, 0] = np.where(keep, first, -1)
+        keep, first = _first_max(ye[:, 1:, :], False)
+        gold[:, 1:, 1] = np.where(keep, first, -1)
+        has = gold[:, 1:, 0] >= 0
+        regular &= (has == kept).all(axis=1) & ((gold[:, 1:, 1] >= 0) == kept).all(axis=1)
+        hit_h = has & (pred[:, 1:, 0] == gold[:, 1:, 0])
+        hit_l = has & (pred[:, 1:, 1] == gold[:, 1:, 1])
+        counts[:, 0] = has.sum(axis=1)
+        counts[:, 1] = (hit_h & hit_l).sum(axis=1)
+        counts[:, 2] = hit_h.sum(axis=1)
+        counts[:, 3] = hit_l.sum(axis=1)
+    counts[:, 4] = regular
+    return pred, gold, counts
+
+
+def scores_from_counts(counts, fallback):
+    """batch_las_uas's (LAS, UAS, label accuracy) from the decode counts
+    [b, 5]: the per-graph quotients in Python ints / floats, added in graph
+    order.  A graph with regular == 0 or n_kept == 0 is scored by
+    ``fallback(i)`` -> (las, uas, label accuracy): the reference's list path
+    (graph_scores on its probabilities, or graph_scores_from_lists), which is
+    what batch_las_uas does with such a graph -- bit-identical."""
+    c = np.asarray(counts)
+    b = c.shape[0]
+    acc_las = acc_uas = acc_uas_e = 0.0
+    for i in range(b):
+        kept, las_n, uas_n, lab_n, regular = (int(x) for x in c[i])
+        if regular and kept > 0:
+            las, uas, uas_e = las_n / kept, uas_n / kept, lab_n / kept
+        else:
+            las, uas, uas_e = fallback(i)
+        acc_las += las
+        acc_uas += uas
+        acc_uas_e += uas_e
+    return acc_las / b, acc_uas / b, acc_uas_e / b
+
+
+def graph_scores(labels, computed_values, mask, labels_e, computed_values_e, mask_e, num_vertices, output_size,
+                 output_size_edges):
+    """One graph ([v*o] / [v*e] rows of a batch's arrays) through the
+    reference's lists: what batch_las_uas does with an irregular graph."""
+    one = lambda a: np.asarray(a)[None]
+    _, res, tgt = results_reshaped_btb(one(labels), one(computed_values), one(mask), num_vertices, output_size,
+                                       output_size_edges)
+    _, res_e, tgt_e = results_reshaped_btb(one(labels_e), one(computed_values_e), one(mask_e), num_vertices,
+                                           output_size, output_size_edges, is_edge=True)
+    return _graph_las_uas(res[0], tgt[0], res_e[0], tgt_e[0])
+
+
+def lists_from_decoded(decoded):
+    """decoded [v, 2] (one graph of decode's pred or gold) -> (head list,
+    label list) as adj_mat_to_target gives them: [[head, 1], ...] and
+    [[0, label], ...] (label one-based) over the nodes that are not skipped."""
+    d = np.asarray(decoded)
+    return [[int(x), 1] for x in d[1:, 0] if x >= 0], [[0, int(x) + 1] for x in d[1:, 1] if x >= 0]
+
+
+def graph_scores_from_lists(pred, gold):
+    """_graph_las_uas from one graph's decoded pred / gold [v, 2] instead of
+    its probabilities (the decode's first maxima are adj_mat_to_target's)."""
+    rg_h, rg_e = lists_from_decoded(pred)
+    tg_h, tg_e = lists_from_decoded(gold)
+    target_graph = merge_head_and_edge_graph(tg_h, tg_e)
+    result_graph = merge_head_and_edge_graph(rg_h, rg_e)
+    las, uas = get_las_uas(target_graph, result_graph)
+    _, uas_e = get_las_uas(tg_e, rg_e, is_edge=True)
+    return las, uas, uas_e
+
+
 def _graph_las_uas(res, tgt, res_e, tgt_e):
     """One graph through the reference's lists (chem_tensorflow_dense.py:1179-1199)."""
     tg_h = adj_mat_to_target(tgt)

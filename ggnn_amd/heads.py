@@ -243,6 +243,42 @@ class OutputHeads:
                        "ggnn_heads_backward")
         return dws, dbs, dhT, dh0
 
+    def decode(self, probs, n_nodes, labels=None):
+        """The predicted tree and the LAS / UAS counts of a batch on the device
+        (ggnn_heads_decode).  probs: [head probabilities [b, v, o], label
+        probabilities [b, v, oe]]; n_nodes: int32 [b] on the device; labels:
+        the two heads' 0/1 targets (same shapes) or None.  Returns (pred
+        [b, v, 2], gold [b, v, 2] or None, counts [b, 5]) as int32 device
+        tensors: zero-based (head, label) columns, -1 = skipped; counts =
+        (n_kept, las, uas, lab, regular) per graph."""
+        p_h, p_l = (_decode_input(t, "probs") for t in probs)
+        b, v, o = p_h.shape
+        oe = p_l.shape[2]
+        if p_l.shape[:2] != (b, v):
+            raise ValueError("probs: head %s and label %s shapes disagree" % (tuple(p_h.shape), tuple(p_l.shape)))
+        dev = p_h.device
+        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
+            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
+        y_h = y_l = gold = None
+        if labels is not None:
+            y_h, y_l = (_decode_input(t, "labels") for t in labels)
+            if y_h.shape != p_h.shape or y_l.shape != p_l.shape:
+                raise ValueError("labels must have the probabilities' shapes")
+            gold = torch.empty(b, v, 2, dtype=torch.int32, device=dev)
+        pred = torch.empty(b, v, 2, dtype=torch.int32, device=dev)
+        counts = torch.empty(b, _lib.DECODE_COUNTS, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_heads_decode(ctypes.byref(d), _ptr(p_h), o, _ptr(p_l), oe, _ptr(y_h), _ptr(y_l),
+                                               _ptr(n_nodes), _ptr(pred), _ptr(gold), _ptr(counts), _stream()),
+                   "ggnn_heads_decode")
+        return pred, gold, counts
+
+
+def _decode_input(t, name):
+    if t.dim() != 3 or t.dtype != torch.float32 or t.device.type != "cuda":
+        raise ValueError("%s must be float32 [b, v, o] tensors on the GPU" % name)
+    return t.contiguous()
+
 
 class EmbedFunction(torch.autograd.Function):
     """h0 = front-end(tables); backward gives the dense table gradients and

@@ -25,6 +25,11 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
   via ``build_loss()``, and ``train_step()`` (loss -> backward -> clip + Adam,
   chem_tensorflow.py:483-506) -- all on the HIP library (``heads.py``).
 
+* not in the reference: ``predict_batch`` / ``parse`` (the predicted tree of a
+  batch / of raw sentences) and ``evaluate_batch(on_device=True)`` /
+  ``score_epoch`` (the scores from per-graph counts), decoded on the device by
+  ``ggnn_heads_decode`` (``csrc/k_decode.h``)
+
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
 """
@@ -408,6 +413,7 @@ class DenseGGNNChemModel(BtbBatching):
                               self.device)
         y_e = self._up_labels_e(np.asarray(self.placeholders["target_values_edges"], np.float32).reshape(b, v, oe),
                                 self.device)
+        self._last_labels = [y_h, y_e]     # (the decode's gold inputs: _decode_forward)
         return [y_h, y_e]
 
     def _target_count(self, task_id=0) -> float:
@@ -659,6 +665,7 @@ class DenseGGNNChemModel(BtbBatching):
         probs = out["probs"]
         self.ops["computed_values"] = probs[0].reshape(b, v * o)
         self.ops["computed_values_edges"] = probs[1].reshape(b, v * oe)
+        self._last_labels = [inp.yh, inp.ye]
         loss = out["loss"]
         if training and not adam:
             self._reduce(fl, all_reduce)
@@ -855,10 +862,31 @@ class DenseGGNNChemModel(BtbBatching):
 
     get_las_uas = staticmethod(_eval.get_las_uas)  # chem_tensorflow_dense.py:1304-1319
 
-    def evaluate_batch(self, feed_dict=None):
+    def evaluate_batch(self, feed_dict=None, on_device=False):
         """(LAS, UAS, label accuracy) of one batch from the heads' probabilities
         (``humanize_batch_results_btb``, chem_tensorflow_dense.py:1160-1215):
-        runs the forward + heads (no dropout) and scores on the host."""
+        runs the forward + heads (no dropout) and scores on the host.
+        on_device: the same three floats from the decode's per-graph counts
+        (ggnn_heads_decode; only [b, 5] int32 leave the device)."""
+        if on_device:
+            r = self._decode_forward(feed_dict, True)
+            ph, b, v = r["ph"], r["b"], r["v"]
+            o, oe = self.params["output_size"], self.output_size_edges
+
+            def fallback(i):
+                # an irregular graph: the reference's lists on its fetched probabilities
+                row = lambda key, w: np.asarray(ph[key], np.float32).reshape(b, v * w)[i]
+                cv = self.ops["computed_values"][i].detach().cpu().numpy()
+                cv_e = self.ops["computed_values_edges"][i].detach().cpu().numpy()
+                return _eval.graph_scores(row("target_values_head", o), cv, row("node_mask", o),
+                                          row("target_values_edges", oe), cv_e, row("node_mask_edges", oe), v, o, oe)
+
+            if r["counts"] is None:          # masks not of get_mask's closed form: the host scorer
+                return self._score_batch()[:3]
+            counts = r["counts"]
+            if isinstance(counts, torch.Tensor):
+                counts = counts.cpu().numpy()
+            return _eval.scores_from_counts(counts, fallback)
         if feed_dict is not None:
             self.feed(feed_dict)
         saved = {k: self.placeholders.get(k) for k in ("out_layer_dropout_keep_prob",)}
@@ -892,6 +920,240 @@ class DenseGGNNChemModel(BtbBatching):
         labels_e = np.asarray(ph["target_values_edges"], np.float32).reshape(b, v * oe)
         las, uas, uas_e = _eval.batch_las_uas(labels, probs, v, mask, labels_e, probs_e, mask_e, o, oe)
         return las, uas, uas_e, labels, probs, mask, labels_e, probs_e, mask_e
+
+    # ------------------------------------------- decoding (ggnn_heads_decode)
+    def _feed_n_nodes(self, ph):
+        """The graphs' node counts of a feed (node_mask_edges row sums /
+        output_size_edges) as int32 [b], or None when the feed's masks are not
+        of get_mask's closed form (the decode kernel rebuilds them from the
+        counts alone)."""
+        b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
+        o, oe = self.params["output_size"], self.output_size_edges
+        if v > o or ph.get("node_mask") is None or ph.get("node_mask_edges") is None:
+            return None
+        m = np.asarray(ph["node_mask"]).reshape(b, v, o)
+        m_e = np.asarray(ph["node_mask_edges"]).reshape(b, v, oe)
+        n = np.rint(m_e.sum(axis=(1, 2)) / oe).astype(np.int32)
+        ref, ref_e = _eval.closed_form_masks(n, v, o, oe)
+        if not (np.array_equal(m, ref) and np.array_equal(m_e, ref_e)):
+            return None
+        return n
+
+    def _decode_forward(self, feed_dict, with_gold):
+        """The dropout-free forward of a feed (through its shape's captured
+        step when _graph_ok, as run_epoch's validation pass) followed by the
+        decode launch on the same stream.  Returns a dict: loss (scalar
+        tensor), ph (the staged placeholders), b, v, n_nodes (host int32 [b],
+        None: masks not in closed form) and pred / gold / counts -- int32
+        device tensors, numpy arrays on a CPU device (decode_arrays), None
+        without n_nodes."""
+        feed = dict(self.placeholders if feed_dict is None else feed_dict)
+        for k in ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weight_dropout_keep_prob",
+                  "emb_dropout_keep_prob"):
+            feed[k] = 1.0
+        loss = None
+        with torch.no_grad():
+            if self._graph_ok(feed):
+                loss = self._graph_step(feed, False)
+            if loss is None:
+                self.graph_stats["eager"] += 1
+                self.feed(feed)
+                loss = self.build_loss()
+        ph = dict(self.placeholders)
+        b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
+        o, oe = self.params["output_size"], self.output_size_edges
+        r = {"loss": loss.detach(), "ph": ph, "b": b, "v": v, "pred": None, "gold": None, "counts": None}
+        n = r["n_nodes"] = self._feed_n_nodes(ph)
+        if n is None:
+            return r
+        probs = self.ops["computed_values"].detach().reshape(b, v, o)
+        probs_e = self.ops["computed_values_edges"].detach().reshape(b, v, oe)
+        if probs.device.type != "cuda":
+            y = y_e = None
+            if with_gold:
+                y = np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o)
+                y_e = np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)
+            r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(probs.numpy(), probs_e.numpy(), n, y, y_e)
+            return r
+        if getattr(self, "_decoder", None) is None:
+            self._decoder, self._up_nodes = OutputHeads(self.params["hidden_size"]), Uploader()
+        r["pred"], r["gold"], r["counts"] = self._decoder.decode(
+            [probs, probs_e], self._up_nodes(n, self.device), self._last_labels if with_gold else None)
+        return r
+
+    def _host_pred(self, ph, b, v):
+        """pred [b, v, 2] of the staged batch from its fetched probabilities and
+        the feed's own masks (a feed whose masks the decode cannot rebuild)."""
+        o, oe = self.params["output_size"], self.output_size_edges
+        cv = self.ops["computed_values"].detach().cpu().numpy()
+        cv_e = self.ops["computed_values_edges"].detach().cpu().numpy()
+        zeros, zeros_e = np.zeros((b, v * o), np.float32), np.zeros((b, v * oe), np.float32)
+        _, res, _ = _eval.results_reshaped_btb(zeros, cv, np.asarray(ph["node_mask"], np.float32).reshape(b, v * o),
+                                               v, o, oe)
+        _, res_e, _ = _eval.results_reshaped_btb(zeros_e, cv_e,
+                                                 np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v * oe),
+                                                 v, o, oe, is_edge=True)
+        pred = np.full((b, v, 2), -1, np.int32)
+        keep, first = _eval._first_max(res[:, 0, 1:, :], True)
+        pred[:, 1:, 0] = np.where(keep, first, -1)
+        keep, first = _eval._first_max(np.transpose(res_e[:, :, 1:, 0], (0, 2, 1)), True)
+        pred[:, 1:, 1] = np.where(keep, first, -1)
+        return pred
+
+    def predict_batch(self, feed_dict=None):
+        """The predicted tree of every graph of a batch: {'heads': [b, v],
+        'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
+        arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
+        prediction: node 0, padding, an all-zero row), 'n_nodes': [b],
+        'sentences_id'}.  Runs the dropout-free forward and decodes on the
+        device; 2 * b * v int32 come back instead of both probability arrays."""
+        r = self._decode_forward(feed_dict, False)
+        ph, b, v = r["ph"], r["b"], r["v"]
+        pred = r["pred"]
+        if pred is None:
+            pred = self._host_pred(ph, b, v)
+            n = np.rint(np.asarray(ph["node_mask_edges"]).reshape(b, -1).sum(axis=1)
+                        / self.output_size_edges).astype(np.int32)
+        else:
+            n = r["n_nodes"]
+            if isinstance(pred, torch.Tensor):
+                pred = pred.cpu().numpy()
+        return {"heads": np.ascontiguousarray(pred[:, :, 0]), "labels": np.ascontiguousarray(pred[:, :, 1]),
+                "n_nodes": n, "sentences_id": ph.get("sentences_id")}
+
+    def parse(self, raw_data):
+        """Parse raw btb sentences (the dicts process_raw_graphs accepts;
+        'targets' may be absent): one entry per input sentence, in input
+        order, in the JSON's own 'targets' form [[head, label], ...] for nodes
+        1..n-1 with the label one-based -- what adj_mat_to_target(...,
+        is_probability=True) + merge_head_and_edge_graph give for the sentence.
+        A sentence process_raw_graphs drops (empty graph) yields []."""
+        raw = []
+        for k, d in enumerate(raw_data):
+            c = dict(d)
+            c.setdefault("targets", [])
+            c["id"] = k                      # (in the copy: the batches carry the input position)
+            raw.append(c)
+        out = [[] for _ in raw]
+        data = self.process_raw_graphs(raw, False)
+        for feed in self.make_minibatch_iterator(data, False):
+            p = self.predict_batch(feed)
+            for k, heads, labels in zip(p["sentences_id"], p["heads"], p["labels"]):
+                rg_h = [[int(x), 1] for x in heads[1:] if x >= 0]
+                rg_e = [[0, int(x) + 1] for x in labels[1:] if x >= 0]
+                out[k] = _eval.merge_head_and_edge_graph(rg_h, rg_e)
+        return out
+
+    def score_epoch(self, data):
+        """The validation pass of run_epoch with the scoring on the device:
+        per batch only the loss and the decode's counts [b, 5] are fetched
+        (pred / gold too for a batch with an irregular graph, scored through
+        the reference's lists; both probability arrays only for a feed whose
+        masks are not in closed form).  One batch in flight and the sums over
+        the ranks as in run_epoch.  Returns (loss, las, uas, label_acc,
+        instances_per_sec, steps) -- run_epoch's values.  ``decode_stats``
+        holds the pass's graphs, host-fallback graphs and fetched bytes."""
+        loss = 0.0
+        processed, steps = 0, 0
+        acc_las = acc_uas = acc_uas_e = 0.0
+        stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0}
+
+        def fetch(r):
+            if r["counts"] is None:          # the host scorer decides: fetch what it reads
+                r["scored"] = self._score_batch()[:3]
+                r["host"] = [r["loss"].cpu()]
+                stats["d2h_bytes"] += 4 + 4 * r["b"] * r["v"] * (self.params["output_size"] + self.output_size_edges)
+                stats["fallback_graphs"] += r["b"]
+                r["event"] = None
+                return r
+            dev = [r["loss"].reshape(1), r["counts"]]
+            if isinstance(dev[1], np.ndarray):   # a CPU device: decode_arrays' counts
+                r["host"], r["event"] = [dev[0], torch.from_numpy(dev[1])], None
+                return r
+            host = [self._pinned_decode(i, t) for i, t in enumerate(dev)]
+            for h, t in zip(host, dev):
+                h.copy_(t, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            stats["d2h_bytes"] += sum(t.numel() * t.element_size() for t in dev)
+            r["host"], r["event"] = host, ev
+            return r
+
+        def consume(r):
+            nonlocal loss, processed, steps, acc_las, acc_uas, acc_uas_e
+            if r["event"] is not None:
+                r["event"].synchronize()
+            b = r["b"]
+            batch_loss = float(r["host"][0].sum())
+            if r["counts"] is None:
+                las, uas, uas_e = r["scored"]
+            else:
+                lists = {}
+
+                def fallback(i):
+                    if not lists:
+                        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+                        lists["pred"], lists["gold"] = as_np(r["pred"]), as_np(r["gold"])
+                        if isinstance(r["pred"], torch.Tensor):
+                            stats["d2h_bytes"] += 2 * lists["pred"].nbytes
+                    stats["fallback_graphs"] += 1
+                    return _eval.graph_scores_from_lists(lists["pred"][i], lists["gold"][i])
+
+                las, uas, uas_e = _eval.scores_from_counts(r["host"][1].numpy(), fallback)
+            stats["graphs"] += b
+            processed += b
+            loss += batch_loss * b
+            acc_las += las * b
+            acc_uas += uas * b
+            acc_uas_e += uas_e * b
+            steps += 1
+
+        start = time.time()
+        pending = None
+        world = self.world_size
+        if world > 1 and _dist.all_reduce_sum(self.group) is None:
+            raise RuntimeError("world_size %d but torch.distributed is not initialised" % world)
+        sched = self.minibatch_schedule(data, False)
+        if world > 1:
+            self._check_schedule_agrees(sched)
+        it = self.make_minibatch_iterator(data, False, rank=self.rank, world_size=world, schedule=sched)
+        for feed in ThreadedIterator(it, max_queue_size=5):
+            if int(feed["num_graphs"]) == 0:     # no batch for this rank in the last global step
+                continue
+            cur = fetch(self._decode_forward(feed, True))
+            if pending is not None:
+                consume(pending)
+            pending = cur
+        if pending is not None:
+            consume(pending)
+        elapsed = time.time() - start
+        if world > 1:
+            dev = self.device if torch.distributed.get_backend(self.group) == "nccl" else torch.device("cpu")
+            tot = torch.tensor([processed, loss, acc_las, acc_uas, acc_uas_e, steps], dtype=torch.float64, device=dev)
+            torch.distributed.all_reduce(tot, group=self.group)
+            mx = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            torch.distributed.all_reduce(mx, op=torch.distributed.ReduceOp.MAX, group=self.group)
+            t = tot.cpu().numpy()
+            processed, loss, acc_las, acc_uas, acc_uas_e, steps = (float(t[0]), float(t[1]), float(t[2]), float(t[3]),
+                                                                   float(t[4]), int(t[5]))
+            elapsed = float(mx.item())
+        processed = max(processed, 1)
+        return (loss / processed, acc_las / processed, acc_uas / processed, acc_uas_e / processed,
+                processed / elapsed, steps)
+
+    def _pinned_decode(self, slot, t):
+        """score_epoch's page-locked fetch buffers (loss, counts): two sets
+        alternate, as _pinned's do, for the one batch in flight."""
+        pool = self.__dict__.setdefault("_pin_pool_decode", {})
+        flip = getattr(self, "_pin_flip_decode", 0)
+        buf = pool.get((slot, flip))
+        n = t.numel()
+        if buf is None or buf.numel() < n or buf.dtype != t.dtype:
+            buf = torch.empty(max(n, 1), dtype=t.dtype, pin_memory=True)
+            pool[(slot, flip)] = buf
+        if slot == 1:
+            self._pin_flip_decode = flip ^ 1
+        return buf[:n].view(t.shape)
 
     def _fetch_batch(self, loss, feed):
         """Queue the device -> host copies of one batch's loss and heads'

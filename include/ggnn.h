@@ -377,6 +377,39 @@ int ggnn_heads_backward_dev(const ggnn_dims* d, const ggnn_output_head* heads, i
                             const float* h0, const float* target_num, const float* d_loss, void* ws,
                             float* dhT, float* dh0, ggnn_stream_t stream);
 
+/* Decoding of the two heads' probabilities on the device: the predicted head
+ * and label of every node and the per-graph LAS / UAS counts, with the host
+ * scorer's semantics (chem_tensorflow_dense.py:1054-1079 get_results_reshaped,
+ * :106-131 adj_mat_to_target).  For graph g with n = n_nodes[g] (clamped to
+ * [0, v]) and node i in 1..v-1:
+ *   pred[g][i][0]  the first maximum over the o columns of probs_head[g][i][j]
+ *                  * (j < n ? 1 : 0); pred[g][i][1] the first maximum over the
+ *                  oe columns of probs_label[g][i][:].  -1 (skipped) when
+ *                  i >= n, the maximum is 0, or the masked row holds a NaN.
+ *   gold[g][i][0 / 1]  the first column of gold_head / gold_label [g][i][:]
+ *                  equal to 1.0f, -1 when there is none (every row 1..v-1).
+ *   counts[g] = { n_kept, las, uas, lab, regular }: the nodes with a gold head,
+ *                  those of them whose predicted head and label / head / label
+ *                  equal the gold ones, and regular = 1 when the four lists
+ *                  (two without gold) skip the same nodes and no input of a
+ *                  row i < n is NaN or +-inf (otherwise the reference's
+ *                  position-wise list comparison differs from these counts:
+ *                  score that graph on the host).
+ * Row 0 of pred / gold is -1.  Values are zero-based column indices.  gold_head
+ * and gold_label are given together or both NULL (then gold is not written and
+ * the counts are 0 but for regular).  Needs v <= o and o, oe in 1..1024.
+ * Stream-ordered, legal under stream capture, bit-reproducible. */
+#define GGNN_DECODE_COUNTS 5 /* n_kept, las, uas, lab, regular */
+int ggnn_heads_decode(const ggnn_dims* d, /* b, v used */
+                      const float* probs_head, int32_t o, const float* probs_label, int32_t oe,
+                      const float* gold_head,  /* [b][v][o]  or NULL */
+                      const float* gold_label, /* [b][v][oe] or NULL */
+                      const int32_t* n_nodes,  /* device [b] */
+                      int32_t* pred,           /* device [b][v][2] out */
+                      int32_t* gold,           /* device [b][v][2] out, or NULL */
+                      int32_t* counts,         /* device [b][GGNN_DECODE_COUNTS] out */
+                      ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */
