@@ -145,6 +145,26 @@ def closed_form_masks(n_nodes, num_vertices, output_size, output_size_edges):
     return r[:, :, None] & c[:, None, :], np.broadcast_to(r[:, :, None], r.shape + (int(output_size_edges),))
 
 
+def _pred_of_masked(res, res_e):
+    """pred [b, v, 2] int32 from masked probabilities [b, v, o] / [b, v, e]:
+    each node row 1..v-1's first maximum, -1 for node 0 and an all-zero row."""
+    pred = np.full(res.shape[:2] + (2,), -1, np.int32)
+    keep, first = _first_max(res[:, 1:, :], True)
+    pred[:, 1:, 0] = np.where(keep, first, -1)
+    keep, first = _first_max(res_e[:, 1:, :], True)
+    pred[:, 1:, 1] = np.where(keep, first, -1)
+    return pred
+
+
+def pred_from_masks(probs, probs_e, mask, mask_e):
+    """decode_arrays' pred for a feed whose masks are not of get_mask's closed
+    form: probs [b, v, o] / probs_e [b, v, e] (or flattened per graph) times
+    the feed's own node_mask / node_mask_edges of the same sizes."""
+    m, m_e = np.asarray(mask, np.float32), np.asarray(mask_e, np.float32)
+    return _pred_of_masked(np.asarray(probs, np.float32).reshape(m.shape) * m,
+                           np.asarray(probs_e, np.float32).reshape(m_e.shape) * m_e)
+
+
 def decode_arrays(probs, probs_e, n_nodes, labels=None, labels_e=None):
     """The host form of ``ggnn_heads_decode`` (include/ggnn.h), written with
     the scorer's own ``_first_max``: probs [b, v, o] and probs_e [b, v, e] are
@@ -167,11 +187,7 @@ def decode_arrays(probs, probs_e, n_nodes, labels=None, labels_e=None):
     m, m_e = closed_form_masks(n, v, o, e)
     with np.errstate(invalid="ignore"):     # (inf * 0: a NaN, as on the reference's path)
         res, res_e = p * m.astype(np.float32), pe * m_e.astype(np.float32)
-    pred = np.full((b, v, 2), -1, np.int32)
-    keep, first = _first_max(res[:, 1:, :], True)
-    pred[:, 1:, 0] = np.where(keep, first, -1)
-    keep, first = _first_max(res_e[:, 1:, :], True)
-    pred[:, 1:, 1] = np.where(keep, first, -1)
+    pred = _pred_of_masked(res, res_e)
     real = m_e[:, 1:, 0]
     bad = ((~np.isfinite(p[:, 1:, :])).any(axis=2) | (~np.isfinite(pe[:, 1:, :])).any(axis=2)) & real
     kept = pred[:, 1:, 0] >= 0

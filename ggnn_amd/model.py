@@ -32,6 +32,17 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
 
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
+
+How the class is laid out: one step body without autograd (``_forward`` on a
+``_StepFeed``; ``_forward_backward`` adds the backward half), which
+``train_step`` runs eagerly and ``_graph_step`` records as a captured step;
+one dropout-free forward behind every evaluation entry but the host branch of
+``evaluate_batch`` (``_eval_forward``: captured if possible, else
+``build_loss``); one epoch loop (``_epoch``) under ``run_epoch`` and
+``score_epoch``, whose per-batch results come back through
+``upload.PinnedFetch``.  All state is declared in
+``prepare_specific_graph_model``; the objects that load libggnn.so are made on
+first use by ``_embedder`` / ``_output_heads`` / ``_decode_heads`` / ``_engine``.
 """
 from __future__ import annotations
 
@@ -51,9 +62,13 @@ from .engine import PropagationEngine
 from .graphs import CapturedStep, PinnedRing, StepLayout, edge_arrays
 from .heads import SMALL_NUMBER, EmbedFunction, EmbeddingFrontEnd, HeadsFunction, OutputHeads, word_inputs_tensor
 from .optim import ClipAdam
-from .upload import Uploader
+from .upload import PinnedFetch, Uploader
 
 GRU_KEYS = ("gates_kernel", "gates_bias", "candidate_kernel", "candidate_bias")
+# the path's weights in the order the engine's dicts and _Propagate take them
+PATH_KEYS = ("edge_weights", "edge_biases") + GRU_KEYS
+KEEP_KEYS = ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weight_dropout_keep_prob",
+             "emb_dropout_keep_prob")
 
 
 def mlp_init(shape, rng):
@@ -87,18 +102,17 @@ class _Propagate(torch.autograd.Function):
     """h_T = GGNN_T(h0; W, beta, GRU) through the HIP engine."""
 
     @staticmethod
-    def forward(ctx, h0, W, beta, Wg, bg, Wc, bc, engine, T, edge_keep=1.0, state_keep=1.0, seed=0):
-        weights = {"edge_weights": W.contiguous(), "edge_biases": beta.contiguous() if beta is not None else None,
-                   "gates_kernel": Wg.contiguous(), "gates_bias": bg.contiguous(),
-                   "candidate_kernel": Wc.contiguous(), "candidate_bias": bc.contiguous()}
+    def forward(ctx, h0, engine, T, edge_keep, state_keep, seed, *path_weights):
+        """path_weights: the six tensors of PATH_KEYS (edge_biases may be None)."""
+        weights = {k: None if w is None else w.contiguous() for k, w in zip(PATH_KEYS, path_weights)}
         pack = engine.pack_weights(weights, T=T, edge_keep=edge_keep, seed=seed, batch=True)
         # (autograd runs Function.forward with grad mode off: ask the ctx)
-        training = any(ctx.needs_input_grad[:7])
+        training = any(ctx.needs_input_grad)
         out = engine.forward(h0.contiguous(), pack, T, training=training, state_keep=state_keep)
         ctx.engine = engine
         ctx.generation = engine.generation
-        ctx.has_beta = beta is not None
-        ctx.beta_shape = None if beta is None else tuple(beta.shape)
+        beta = weights["edge_biases"]
+        ctx.beta_shape = None if beta is None else tuple(path_weights[1].shape)
         ctx.pack = pack
         return out
 
@@ -109,11 +123,11 @@ class _Propagate(torch.autograd.Function):
             raise RuntimeError("the engine ran another forward since this output was produced; "
                                "call backward before re-using the same call site")
         g = eng.backward(g_out.contiguous())
-        db = g["edge_biases"]
-        if ctx.has_beta and db is not None:
-            db = db.view(ctx.beta_shape)
-        return (g["h0"], g["edge_weights"], db if ctx.has_beta else None, g["gates_kernel"], g["gates_bias"],
-                g["candidate_kernel"], g["candidate_bias"], None, None, None, None, None)
+        if ctx.beta_shape is None:
+            g["edge_biases"] = None
+        elif g["edge_biases"] is not None:
+            g["edge_biases"] = g["edge_biases"].view(ctx.beta_shape)
+        return (g["h0"], None, None, None, None, None) + tuple(g[k] for k in PATH_KEYS)
 
 
 class DenseGGNNChemModel(BtbBatching):
@@ -221,14 +235,25 @@ class DenseGGNNChemModel(BtbBatching):
                                 ("regression_transform_task_edges%i", [h, oe])):
                 self.weights[name % task_id] = {"weights": [t(mlp_init(shape, self._rng))],
                                                 "biases": [t(np.zeros([shape[1]], np.float32))]}
+        # the library's front-end, the eager path's heads and the decoder load
+        # libggnn.so: created on first use (_embedder, _output_heads, _decode_heads)
         self._front_end = None
         self._heads = None
+        self._decoder = None
+        self._up_nodes = Uploader()
+        self._last_labels = None   # the last forward's labels on the device: the decode's gold inputs
+        # the last forward's dropout draws, by stage (keep probabilities, seed, ...)
+        self.last_embed = self.last_dropout = self.last_heads = None
+        # the epoch loops' device -> host fetches: run_epoch's (loss, both
+        # heads' probabilities) and score_epoch's (loss, decode counts)
+        self._fetch_probs, self._fetch_counts = PinnedFetch(), PinnedFetch()
+        self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0}
         self._flat = None
         self._rows = None          # the word segment's lookup rows / ids (sparse data-parallel reduction)
         # hipGraph-captured steps by batch shape (graphs.py), least recently
         # used first; bounded by params['hip_graph_cache_mb'] (_evict_graphs)
         self._graphs = OrderedDict()
-        self._ring = None
+        self._ring = PinnedRing()
         # batches by path: captured-step replays, first batches of a shape
         # (eager, on the step's device inputs), the plain eager path
         self.graph_stats = {"captured": 0, "replayed": 0, "uncaptured": 0, "eager": 0, "evicted": 0, "cache_bytes": 0}
@@ -242,6 +267,31 @@ class DenseGGNNChemModel(BtbBatching):
         single process, keep the plain draw)."""
         s = int(self._rng.randint(0, 2 ** 31 - 1)) << 32 | int(self._rng.randint(0, 2 ** 31 - 1))
         return s ^ ((self.rank * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF)
+
+    def _embedder(self) -> EmbeddingFrontEnd:
+        if self._front_end is None:
+            self._front_end = EmbeddingFrontEnd(self.params["hidden_size"])
+        return self._front_end
+
+    def _output_heads(self) -> OutputHeads:
+        """The eager path's heads (a captured step has its own workspace)."""
+        if self._heads is None:
+            self._heads = OutputHeads(self.params["hidden_size"])
+        return self._heads
+
+    def _decode_heads(self) -> OutputHeads:
+        if self._decoder is None:
+            self._decoder = OutputHeads(self.params["hidden_size"])
+        return self._decoder
+
+    def _path_weights(self, fixed=False) -> dict:
+        """The path's six weights (PATH_KEYS) as the dict the engine takes;
+        ``fixed``: the ``*_fixed`` edge weights / biases."""
+        W, sfx = self.weights, "_fixed" if fixed else ""
+        wts = {"edge_weights": W["edge_weights" + sfx],
+               "edge_biases": W["edge_biases" + sfx] if self.params["use_edge_bias"] else None}
+        wts.update((k, W["node_gru"][k]) for k in GRU_KEYS)
+        return wts
 
     def parameters(self):
         ps = [self.weights["edge_weights"], self.weights["edge_weights_fixed"]]
@@ -275,7 +325,6 @@ class DenseGGNNChemModel(BtbBatching):
             if feed_dict.get("adjacency_edges") is None:
                 raise ValueError("feed needs adjacency_matrix or adjacency_edges")
             self.placeholders["adjacency_matrix"] = None
-            self._fed = False
             return
         if not isinstance(adj, torch.Tensor):
             adj = torch.from_numpy(np.ascontiguousarray(np.asarray(adj, dtype=np.float32)))
@@ -286,16 +335,17 @@ class DenseGGNNChemModel(BtbBatching):
             raise ValueError("adjacency has %d channels, model expects 2*num_edge_types = %d" % (C, self.num_channels))
         if int(feed_dict.get("num_vertices", v)) != v or int(feed_dict.get("num_graphs", b)) != b:
             raise ValueError("num_vertices/num_graphs disagree with adjacency shape %s" % (tuple(adj.shape),))
-        self._fed = False
 
     def _engine(self, site):
         key = (self.params["hidden_size"], self.num_channels, bool(self.params["use_edge_bias"]), site)
         eng = self._engines.get(key)
         if eng is None:
-            eng = PropagationEngine(key[0], key[1], key[2], device=self.device,
-                                    precision=self.precision)  # one per call site
-            self._engines[key] = eng
+            eng = self._engines[key] = self._new_engine()      # one per call site
         return eng
+
+    def _new_engine(self) -> PropagationEngine:
+        return PropagationEngine(self.params["hidden_size"], self.num_channels, bool(self.params["use_edge_bias"]),
+                                 device=self.device, precision=self.precision)
 
     # ------------------------------------------------------------ hot path
     def compute_final_node_representations(self, initial_node_representations, fixed_ts=None):
@@ -315,23 +365,17 @@ class DenseGGNNChemModel(BtbBatching):
         # (:396-412); compute_timestep_normal (--old, :350-389) always uses the
         # main edge_weights / edge_biases
         fixed = fixed_ts is not None and not self.args.get("--old")
-        W = self.weights["edge_weights_fixed"] if fixed else self.weights["edge_weights"]
-        beta = None
-        if self.params["use_edge_bias"]:
-            beta = self.weights["edge_biases_fixed"] if fixed else self.weights["edge_biases"]
         h0 = initial_node_representations
         if not isinstance(h0, torch.Tensor):
             h0 = torch.from_numpy(np.ascontiguousarray(np.asarray(h0, dtype=np.float32)))
         h0 = h0.to(device=self.device, dtype=torch.float32)
         eng = self._engine("main" if fixed_ts is None else "fixed")
         self._stage_adjacency(eng)
-        gru = self.weights["node_gru"]
         # dropout as fed (chem_tensorflow_dense.py:860-861 training, :938-940 eval);
         # a fresh Philox seed per call = fresh masks per step, like TF's stateful RNG
         edge_keep, state_keep = self._path_keeps()
         seed = self._seed()
-        out = _Propagate.apply(h0, W, beta, gru["gates_kernel"], gru["gates_bias"],
-                               gru["candidate_kernel"], gru["candidate_bias"], eng, T, edge_keep, state_keep, seed)
+        out = _Propagate.apply(h0, eng, T, edge_keep, state_keep, seed, *self._path_weights(fixed).values())
         self.last_dropout = dict(edge_keep=edge_keep, state_keep=state_keep, seed=seed)
         self.ops["final_node_representations" if fixed_ts is None else "second_node_representations"] = out
         return out
@@ -362,19 +406,13 @@ class DenseGGNNChemModel(BtbBatching):
         looked up by the reference but unused; they are not gathered here."""
         if "word_inputs" not in self.placeholders:
             raise RuntimeError("feed() a minibatch with word_inputs first")
-        h = self.params["hidden_size"]
-        width = self.loc_embedding_size * 2 + self.pos_embedding_size + self.word_embedding_size
-        if width > h:
-            raise ValueError("embedding concat width %d > hidden_size %d: the reference's tf.pad fails here "
-                             "(SURVEY F7); pass smaller embedding_sizes" % (width, h))
+        self._check_front_end_width()
         tables, cols = self._front_end_segments()
         wi = word_inputs_tensor(self.placeholders["word_inputs"], self.device,
                                 {c: tb.shape[0] for tb, c in zip(tables, cols)})
         keep = float(self.placeholders.get("emb_dropout_keep_prob", 1.0))
         seed = self._seed()
-        if self._front_end is None:
-            self._front_end = EmbeddingFrontEnd(h)
-        h0 = EmbedFunction.apply(self._front_end, self, wi, keep, seed, cols, *tables)
+        h0 = EmbedFunction.apply(self._embedder(), self, wi, keep, seed, cols, *tables)
         self.last_embed = dict(keep=keep, seed=seed)
         self.ops["initial_node_representations"] = h0
         return h0
@@ -385,18 +423,15 @@ class DenseGGNNChemModel(BtbBatching):
         over task_target_num = sum(target_mask[task]) + SMALL_NUMBER."""
         h0 = self.get_initial_node_representation()
         hT = self.compute_final_node_representations(h0)
-        b, v, h = hT.shape
+        b, v, _ = hT.shape
         o, oe = self.params["output_size"], self.output_size_edges
         labels = self._head_labels(b, v)
         target_num = float(self._target_count(task_id) + SMALL_NUMBER)
         keep = self._out_keep()
         seed = self._seed()
-        if self._heads is None:
-            self._heads = OutputHeads(h)
-        g = self.weights["regression_gate_task%i" % task_id]
-        ge = self.weights["regression_gate_task_edges%i" % task_id]
-        loss, probs, probs_e = HeadsFunction.apply(self._heads, labels, keep, seed, target_num, hT, h0,
-                                                   g["weights"][0], g["biases"][0], ge["weights"][0], ge["biases"][0])
+        (gw, gb), (gew, geb) = self._heads_list(task_id)
+        loss, probs, probs_e = HeadsFunction.apply(self._output_heads(), labels, keep, seed, target_num, hT, h0,
+                                                   gw, gb, gew, geb)
         self.ops["loss"] = loss
         self.ops["computed_values"] = probs.reshape(b, v * o)
         self.ops["computed_values_edges"] = probs_e.reshape(b, v * oe)
@@ -486,13 +521,11 @@ class DenseGGNNChemModel(BtbBatching):
         if sparse:
             rows, ids = self._lookup_rows()
             g_rows, g_ids = reducer.gather(rows), reducer.gather(ids)
-            if self._front_end is None:
-                self._front_end = EmbeddingFrontEnd(self.params["hidden_size"])
             word = self.weights["word_embeddings"]
             tables = self._front_end_segments()[0]
             slot = next(i for i, t in enumerate(tables) if t is word)
-            self._front_end.union_backward(word, fl.grads[fl.sparse[0]], g_rows.view(-1, word.shape[1]),
-                                           g_ids.view(-1), fl.sq[slot:slot + 1])
+            self._embedder().union_backward(word, fl.grads[fl.sparse[0]], g_rows.view(-1, word.shape[1]),
+                                            g_ids.view(-1), fl.sq[slot:slot + 1])
 
     def train_step(self, feed_dict=None, grad_scale=1.0, all_reduce=None, target_count=None, task_id=0):
         """One training step (chem_tensorflow.py:483-506 + run_epoch's
@@ -600,11 +633,8 @@ class DenseGGNNChemModel(BtbBatching):
                 self.make_optimizer()
         cs = self._graphs.get(key)
         if cs is None:
-            eng = PropagationEngine(self.params["hidden_size"], self.num_channels, bool(self.params["use_edge_bias"]),
-                                    device=self.device, precision=self.precision)
-            cs = CapturedStep(StepLayout(b, v, wi.shape[-1], o, oe), eng, OutputHeads(self.params["hidden_size"]),
-                              self.device)
-            self._graphs[key] = cs
+            cs = self._graphs[key] = CapturedStep(StepLayout(b, v, wi.shape[-1], o, oe), self._new_engine(),
+                                                  OutputHeads(self.params["hidden_size"]), self.device)
         self._graphs.move_to_end(key)
         seeds = [self._seed() for _ in range(3)]
         step = 0
@@ -613,8 +643,6 @@ class DenseGGNNChemModel(BtbBatching):
             step = self.optimizer.t
         # stage the batch: pinned host buffer -> the step's device inputs
         L = cs.layout
-        if self._ring is None:
-            self._ring = PinnedRing()
         i, host = self._ring.acquire(L.nbytes)
         L.fill(host.numpy(), seeds, step, target_num, wi.astype(np.int32), edges, offs,
                np.asarray(ph["target_values_head"], np.float32), np.asarray(ph["target_values_edges"], np.float32))
@@ -636,7 +664,8 @@ class DenseGGNNChemModel(BtbBatching):
                     self._apply_gradients(fl, params, grad_scale, step_dev=inp.step)
                 loss = fl.loss.sum()
             else:
-                probs, loss = self._forward_eval(sf, task_id)
+                _, _, probs, loss = self._forward(sf, task_id, training=False)
+                loss = loss.sum()
             return {"loss": loss, "probs": probs}
 
         if cs.graph is None and cs.runs == 0:
@@ -696,34 +725,29 @@ class DenseGGNNChemModel(BtbBatching):
             self.graph_stats["evicted"] += 1
         self.graph_stats["cache_bytes"] = int(total)
 
-    def _forward_eval(self, sf, task_id=0):
-        """build_loss's forward without autograd on a _StepFeed: front-end ->
-        T-step forward -> heads + btb loss.  Returns (probs, loss sum)."""
-        h = self.params["hidden_size"]
-        tables, cols = self._front_end_segments()
+    def _forward(self, sf, task_id, training, loss_out=None):
+        """The forward of one step on a _StepFeed, without autograd: front-end
+        (chem_tensorflow_dense.py:264-306) -> T-step propagation (:312-340) ->
+        heads + btb loss (:439-516, chem_tensorflow.py:326-421).  ``training``
+        keeps what the engine's backward reads; ``loss_out``: where the heads
+        write the two losses.  Returns (h0, hT, probs, the two heads' losses)."""
+        segs = list(zip(*self._front_end_segments()))
         keep_e = float(self.placeholders.get("emb_dropout_keep_prob", 1.0))
-        if self._front_end is None:
-            self._front_end = EmbeddingFrontEnd(h)
-        h0 = self._front_end.forward(list(zip(tables, cols)), sf.wi, keep_e, sf.seeds[0], seed_device=sf.seed_device)
+        h0 = self._embedder().forward(segs, sf.wi, keep_e, sf.seeds[0], seed_device=sf.seed_device)
         self.last_embed = dict(keep=keep_e, seed=sf.seed_values[0])
         T = self.params["num_timesteps"]
         eng = sf.engine
         sf.stage(eng)
         edge_keep, state_keep = self._path_keeps()
-        W, gru = self.weights, self.weights["node_gru"]
-        wts = {"edge_weights": W["edge_weights"],
-               "edge_biases": W["edge_biases"] if self.params["use_edge_bias"] else None,
-               "gates_kernel": gru["gates_kernel"], "gates_bias": gru["gates_bias"],
-               "candidate_kernel": gru["candidate_kernel"], "candidate_bias": gru["candidate_bias"]}
-        pack = eng.pack_weights(wts, T=T, edge_keep=edge_keep, seed=sf.seeds[1], seed_device=sf.seed_device,
-                                batch=True)
-        hT = eng.forward(h0, pack, T, training=False, state_keep=state_keep)
+        pack = eng.pack_weights(self._path_weights(), T=T, edge_keep=edge_keep, seed=sf.seeds[1],
+                                seed_device=sf.seed_device, batch=True)
+        hT = eng.forward(h0, pack, T, training=training, state_keep=state_keep)
         self.last_dropout = dict(edge_keep=edge_keep, state_keep=state_keep, seed=sf.seed_values[1])
         keep_o = self._out_keep()
         probs, loss = sf.heads.forward(hT, h0, self._heads_list(task_id), sf.labels, keep_o, sf.seeds[2],
-                                       sf.target_num, seed_device=sf.seed_device)
+                                       sf.target_num, loss_out=loss_out, seed_device=sf.seed_device)
         self.last_heads = dict(keep=keep_o, seed=sf.seed_values[2], target_num=sf.target_num_value)
-        return probs, loss.sum()
+        return h0, hT, probs, loss
 
     def _apply_gradients(self, fl, params, grad_scale, step_dev=None):
         if self.optimizer is None:
@@ -750,10 +774,8 @@ class DenseGGNNChemModel(BtbBatching):
         b, v = int(self.placeholders["num_graphs"]), int(self.placeholders["num_vertices"])
         labels = self._head_labels(b, v)
         count = self._target_count(task_id) if target_count is None else target_count
-        if self._heads is None:
-            self._heads = OutputHeads(self.params["hidden_size"])
         return _StepFeed(wi, seeds, seeds, False, labels, float(count + SMALL_NUMBER), self._engine("main"),
-                         self._heads, self._stage_adjacency, b, v)
+                         self._output_heads(), self._stage_adjacency, b, v)
 
     def _check_front_end_width(self):
         width = self.loc_embedding_size * 2 + self.pos_embedding_size + self.word_embedding_size
@@ -783,64 +805,37 @@ class DenseGGNNChemModel(BtbBatching):
             if sf.b * sf.v > cap:
                 raise ValueError("batch of %d x %d nodes exceeds the word lookup-row capacity %d (batch_size x "
                                  "bucket_max_nodes)" % (sf.b, sf.v, cap))
-        h = self.params["hidden_size"]
-        gv = {id(p): g for p, g in zip(params, fl.grads)}
-        # front-end (chem_tensorflow_dense.py:264-306)
-        tables, cols = self._front_end_segments()
-        keep_e = float(self.placeholders.get("emb_dropout_keep_prob", 1.0))
-        if self._front_end is None:
-            self._front_end = EmbeddingFrontEnd(h)
-        segs = list(zip(tables, cols))
-        h0 = self._front_end.forward(segs, sf.wi, keep_e, sf.seeds[0], seed_device=sf.seed_device)
-        self.last_embed = dict(keep=keep_e, seed=sf.seed_values[0])
-        self.ops["initial_node_representations"] = h0
-        # propagation (chem_tensorflow_dense.py:312-340)
-        T = self.params["num_timesteps"]
-        eng = sf.engine
-        sf.stage(eng)
-        edge_keep, state_keep = self._path_keeps()
-        W, gru = self.weights, self.weights["node_gru"]
-        beta = W["edge_biases"] if self.params["use_edge_bias"] else None
-        wts = {"edge_weights": W["edge_weights"], "edge_biases": beta, "gates_kernel": gru["gates_kernel"],
-               "gates_bias": gru["gates_bias"], "candidate_kernel": gru["candidate_kernel"],
-               "candidate_bias": gru["candidate_bias"]}
-        pack = eng.pack_weights(wts, T=T, edge_keep=edge_keep, seed=sf.seeds[1], seed_device=sf.seed_device,
-                                batch=True)
-        hT = eng.forward(h0, pack, T, training=True, state_keep=state_keep)
-        self.last_dropout = dict(edge_keep=edge_keep, state_keep=state_keep, seed=sf.seed_values[1])
-        self.ops["final_node_representations"] = hT
-        # heads + btb loss (chem_tensorflow_dense.py:439-516, chem_tensorflow.py:326-421)
+        h0, hT, probs, _ = self._forward(sf, task_id, training=True, loss_out=fl.loss)
         b, v, _ = hT.shape
         o, oe = self.params["output_size"], self.output_size_edges
-        keep_o = self._out_keep()
-        hl = self._heads_list(task_id)
-        probs, _ = sf.heads.forward(hT, h0, hl, sf.labels, keep_o, sf.seeds[2], sf.target_num, loss_out=fl.loss,
-                                    seed_device=sf.seed_device)
-        self.last_heads = dict(keep=keep_o, seed=sf.seed_values[2], target_num=sf.target_num_value)
+        self.ops["initial_node_representations"], self.ops["final_node_representations"] = h0, hT
         self.ops["computed_values"] = probs[0].reshape(b, v * o)
         self.ops["computed_values_edges"] = probs[1].reshape(b, v * oe)
+        gv = {id(p): g for p, g in zip(params, fl.grads)}
+        hl = self._heads_list(task_id)
         _, _, dhT, dh0_heads = sf.heads.backward(hT, h0, hl, sf.labels, probs, sf.target_num,
                                                   dws=[gv[id(w)] for w, _ in hl], dbs=[gv[id(bb)] for _, bb in hl])
         if reducer is not None and started is not None and hasattr(reducer, "start"):
             # the heads' gradients and the losses are final: their reduction
             # runs on the collective's stream while the propagation backward runs
             started.append(reducer.start(fl.buckets[0]))
-        # the path's backward (TF autodiff, chem_tensorflow.py:496)
-        eg = {"h0": torch.empty_like(h0), "edge_weights": gv[id(W["edge_weights"])],
-              "edge_biases": gv[id(beta)] if beta is not None else None,
-              "gates_kernel": gv[id(gru["gates_kernel"])], "gates_bias": gv[id(gru["gates_bias"])],
-              "candidate_kernel": gv[id(gru["candidate_kernel"])], "candidate_bias": gv[id(gru["candidate_bias"])]}
-        eng.backward(dhT, eg)
+        # the path's backward (TF autodiff, chem_tensorflow.py:496) into the weights' views of the buffer
+        eg = {k: None if w is None else gv[id(w)] for k, w in self._path_weights().items()}
+        eg["h0"] = torch.empty_like(h0)
+        sf.engine.backward(dhT, eg)
         # the tables' gradients + IndexedSlices norms (h0 feeds the path and the heads)
+        tables, cols = self._front_end_segments()
+        segs, keep_e = list(zip(tables, cols)), self.last_embed["keep"]
         word = self.weights["word_embeddings"]
         dts = [None if (sparse and t is word) else gv[id(t)] for t in tables]
-        self._front_end.backward(segs, sf.wi, eg["h0"], keep_e, sf.seeds[0], dh0_add=dh0_heads,
-                                 dtables=dts, sq_out=fl.sq, seed_device=sf.seed_device)
+        self._embedder().backward(segs, sf.wi, eg["h0"], keep_e, sf.seeds[0], dh0_add=dh0_heads,
+                                  dtables=dts, sq_out=fl.sq, seed_device=sf.seed_device)
         if sparse:
             # the word table as IndexedSlices (rows, ids): all-gathered by _reduce
             rows, ids = self._lookup_rows()
-            self._front_end.lookup_rows(segs, next(i for i, t in enumerate(tables) if t is word), sf.wi, eg["h0"], keep_e, sf.seeds[0], rows, ids,
-                                        dh0_add=dh0_heads, seed_device=sf.seed_device)
+            slot = next(i for i, t in enumerate(tables) if t is word)
+            self._embedder().lookup_rows(segs, slot, sf.wi, eg["h0"], keep_e, sf.seeds[0], rows, ids,
+                                         dh0_add=dh0_heads, seed_device=sf.seed_device)
         return probs
 
     def make_optimizer(self) -> ClipAdam:
@@ -889,17 +884,18 @@ class DenseGGNNChemModel(BtbBatching):
             return _eval.scores_from_counts(counts, fallback)
         if feed_dict is not None:
             self.feed(feed_dict)
-        saved = {k: self.placeholders.get(k) for k in ("out_layer_dropout_keep_prob",)}
+        # the staged placeholders as fed, only the output layer's dropout off
+        # (the other keeps are the caller's), never through a captured step
+        saved = self.placeholders.get("out_layer_dropout_keep_prob")
         self.placeholders["out_layer_dropout_keep_prob"] = 1.0
         try:
             with torch.no_grad():
                 self.build_loss()
         finally:
-            for k, v in saved.items():
-                if v is None:
-                    self.placeholders.pop(k, None)
-                else:
-                    self.placeholders[k] = v
+            if saved is None:
+                self.placeholders.pop("out_layer_dropout_keep_prob", None)
+            else:
+                self.placeholders["out_layer_dropout_keep_prob"] = saved
         return self._score_batch()[:3]
 
     def _score_batch(self):
@@ -939,26 +935,28 @@ class DenseGGNNChemModel(BtbBatching):
             return None
         return n
 
+    def _eval_forward(self, feed):
+        """The dropout-free forward of a feed (a copy of it with the four keep
+        probabilities at 1.0 is staged): through its shape's captured step
+        when _graph_ok, else build_loss on the eager path.  Returns the loss."""
+        feed = dict(feed)
+        feed.update((k, 1.0) for k in KEEP_KEYS)
+        with torch.no_grad():
+            loss = self._graph_step(feed, False) if self._graph_ok(feed) else None
+            if loss is None:
+                self.graph_stats["eager"] += 1
+                self.feed(feed)
+                loss = self.build_loss()
+        return loss
+
     def _decode_forward(self, feed_dict, with_gold):
-        """The dropout-free forward of a feed (through its shape's captured
-        step when _graph_ok, as run_epoch's validation pass) followed by the
+        """_eval_forward of a feed (default: the staged one) followed by the
         decode launch on the same stream.  Returns a dict: loss (scalar
         tensor), ph (the staged placeholders), b, v, n_nodes (host int32 [b],
         None: masks not in closed form) and pred / gold / counts -- int32
         device tensors, numpy arrays on a CPU device (decode_arrays), None
         without n_nodes."""
-        feed = dict(self.placeholders if feed_dict is None else feed_dict)
-        for k in ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weight_dropout_keep_prob",
-                  "emb_dropout_keep_prob"):
-            feed[k] = 1.0
-        loss = None
-        with torch.no_grad():
-            if self._graph_ok(feed):
-                loss = self._graph_step(feed, False)
-            if loss is None:
-                self.graph_stats["eager"] += 1
-                self.feed(feed)
-                loss = self.build_loss()
+        loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
         ph = dict(self.placeholders)
         b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
         o, oe = self.params["output_size"], self.output_size_edges
@@ -975,9 +973,7 @@ class DenseGGNNChemModel(BtbBatching):
                 y_e = np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)
             r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(probs.numpy(), probs_e.numpy(), n, y, y_e)
             return r
-        if getattr(self, "_decoder", None) is None:
-            self._decoder, self._up_nodes = OutputHeads(self.params["hidden_size"]), Uploader()
-        r["pred"], r["gold"], r["counts"] = self._decoder.decode(
+        r["pred"], r["gold"], r["counts"] = self._decode_heads().decode(
             [probs, probs_e], self._up_nodes(n, self.device), self._last_labels if with_gold else None)
         return r
 
@@ -985,20 +981,10 @@ class DenseGGNNChemModel(BtbBatching):
         """pred [b, v, 2] of the staged batch from its fetched probabilities and
         the feed's own masks (a feed whose masks the decode cannot rebuild)."""
         o, oe = self.params["output_size"], self.output_size_edges
-        cv = self.ops["computed_values"].detach().cpu().numpy()
-        cv_e = self.ops["computed_values_edges"].detach().cpu().numpy()
-        zeros, zeros_e = np.zeros((b, v * o), np.float32), np.zeros((b, v * oe), np.float32)
-        _, res, _ = _eval.results_reshaped_btb(zeros, cv, np.asarray(ph["node_mask"], np.float32).reshape(b, v * o),
-                                               v, o, oe)
-        _, res_e, _ = _eval.results_reshaped_btb(zeros_e, cv_e,
-                                                 np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v * oe),
-                                                 v, o, oe, is_edge=True)
-        pred = np.full((b, v, 2), -1, np.int32)
-        keep, first = _eval._first_max(res[:, 0, 1:, :], True)
-        pred[:, 1:, 0] = np.where(keep, first, -1)
-        keep, first = _eval._first_max(np.transpose(res_e[:, :, 1:, 0], (0, 2, 1)), True)
-        pred[:, 1:, 1] = np.where(keep, first, -1)
-        return pred
+        return _eval.pred_from_masks(self.ops["computed_values"].detach().cpu().numpy(),
+                                     self.ops["computed_values_edges"].detach().cpu().numpy(),
+                                     np.asarray(ph["node_mask"], np.float32).reshape(b, v, o),
+                                     np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
 
     def predict_batch(self, feed_dict=None):
         """The predicted tree of every graph of a batch: {'heads': [b, v],
@@ -1053,40 +1039,28 @@ class DenseGGNNChemModel(BtbBatching):
         the ranks as in run_epoch.  Returns (loss, las, uas, label_acc,
         instances_per_sec, steps) -- run_epoch's values.  ``decode_stats``
         holds the pass's graphs, host-fallback graphs and fetched bytes."""
-        loss = 0.0
-        processed, steps = 0, 0
-        acc_las = acc_uas = acc_uas_e = 0.0
         stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0}
 
-        def fetch(r):
+        def step(feed, all_reduce):
+            r = self._decode_forward(feed, True)
+            r["event"] = None
             if r["counts"] is None:          # the host scorer decides: fetch what it reads
                 r["scored"] = self._score_batch()[:3]
                 r["host"] = [r["loss"].cpu()]
                 stats["d2h_bytes"] += 4 + 4 * r["b"] * r["v"] * (self.params["output_size"] + self.output_size_edges)
                 stats["fallback_graphs"] += r["b"]
-                r["event"] = None
-                return r
-            dev = [r["loss"].reshape(1), r["counts"]]
-            if isinstance(dev[1], np.ndarray):   # a CPU device: decode_arrays' counts
-                r["host"], r["event"] = [dev[0], torch.from_numpy(dev[1])], None
-                return r
-            host = [self._pinned_decode(i, t) for i, t in enumerate(dev)]
-            for h, t in zip(host, dev):
-                h.copy_(t, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            stats["d2h_bytes"] += sum(t.numel() * t.element_size() for t in dev)
-            r["host"], r["event"] = host, ev
+            elif isinstance(r["counts"], np.ndarray):   # a CPU device: decode_arrays' counts
+                r["host"] = [r["loss"].reshape(1), torch.from_numpy(r["counts"])]
+            else:
+                dev = [r["loss"].reshape(1), r["counts"]]
+                r["host"], r["event"] = self._fetch_counts.fetch(dev)
+                stats["d2h_bytes"] += sum(t.numel() * t.element_size() for t in dev)
             return r
 
         def consume(r):
-            nonlocal loss, processed, steps, acc_las, acc_uas, acc_uas_e
-            if r["event"] is not None:
-                r["event"].synchronize()
-            b = r["b"]
             batch_loss = float(r["host"][0].sum())
             if r["counts"] is None:
-                las, uas, uas_e = r["scored"]
+                scores = r["scored"]
             else:
                 lists = {}
 
@@ -1099,107 +1073,76 @@ class DenseGGNNChemModel(BtbBatching):
                     stats["fallback_graphs"] += 1
                     return _eval.graph_scores_from_lists(lists["pred"][i], lists["gold"][i])
 
-                las, uas, uas_e = _eval.scores_from_counts(r["host"][1].numpy(), fallback)
-            stats["graphs"] += b
-            processed += b
-            loss += batch_loss * b
-            acc_las += las * b
-            acc_uas += uas * b
-            acc_uas_e += uas_e * b
-            steps += 1
+                scores = _eval.scores_from_counts(r["host"][1].numpy(), fallback)
+            stats["graphs"] += r["b"]
+            return (r["b"], batch_loss) + tuple(scores)
+
+        processed, loss, las, uas, uas_e, steps, _, elapsed = self._epoch(data, False, step, consume)
+        return loss / processed, las / processed, uas / processed, uas_e / processed, processed / elapsed, steps
+
+    def _epoch(self, data, is_training, step, consume, extra=None, announce=None):
+        """One pass over ``data``: what run_epoch and score_epoch share.  The
+        epoch's schedule (checked to agree across the ranks), this rank's share
+        of it built in a background thread (ThreadedIterator, max_queue_size
+        5), and one batch in flight: ``step(feed, all_reduce)`` queues a
+        batch's device work and device -> host copies and returns a dict whose
+        'event' (or None) follows them; ``consume(batch)`` -> (graphs, loss,
+        LAS, UAS, label accuracy) of it runs after the NEXT batch's step, so
+        the host's scoring overlaps the GPU instead of alternating with it
+        (the reference's sess.run returns every fetch before the host
+        continues, chem_tensorflow.py:594).  A rank without a batch in the
+        last global step only joins a training step's all-reduce.
+        ``extra()``: more sums of the epoch to add over the ranks; ``announce``:
+        the epoch name to print progress under.  Returns (graphs, loss, LAS,
+        UAS, label accuracy, batches, extra, elapsed): graph-weighted sums over
+        all ranks, at least one graph, the slowest rank's seconds."""
+        tot = [0, 0.0, 0.0, 0.0, 0.0, 0]
+
+        def finish(p):
+            if p["event"] is not None:
+                p["event"].synchronize()
+            b, batch_loss, las, uas, uas_e = consume(p)
+            tot[0] += b
+            for i, x in enumerate((batch_loss, las, uas, uas_e), 1):
+                tot[i] += x * b
+            if announce:
+                print("Running %s, batch %i (has %i graphs). Loss so far: %.4f" % (
+                    announce, tot[5], b, tot[1] / tot[0]), end="\r")
+            tot[5] += 1
 
         start = time.time()
         pending = None
         world = self.world_size
-        if world > 1 and _dist.all_reduce_sum(self.group) is None:
+        all_reduce = _dist.all_reduce_sum(self.group) if world > 1 else None
+        if world > 1 and all_reduce is None:
             raise RuntimeError("world_size %d but torch.distributed is not initialised" % world)
-        sched = self.minibatch_schedule(data, False)
+        sched = self.minibatch_schedule(data, is_training)
         if world > 1:
             self._check_schedule_agrees(sched)
-        it = self.make_minibatch_iterator(data, False, rank=self.rank, world_size=world, schedule=sched)
+        it = self.make_minibatch_iterator(data, is_training, rank=self.rank, world_size=world, schedule=sched)
         for feed in ThreadedIterator(it, max_queue_size=5):
             if int(feed["num_graphs"]) == 0:     # no batch for this rank in the last global step
+                if is_training:
+                    self.train_step(feed, all_reduce=all_reduce)
                 continue
-            cur = fetch(self._decode_forward(feed, True))
+            cur = step(feed, all_reduce)
             if pending is not None:
-                consume(pending)
+                finish(pending)
             pending = cur
         if pending is not None:
-            consume(pending)
+            finish(pending)
         elapsed = time.time() - start
+        more = extra() if extra is not None else np.zeros(0)
         if world > 1:
+            # one reduction of the epoch's sums over the ranks (off the step loop)
             dev = self.device if torch.distributed.get_backend(self.group) == "nccl" else torch.device("cpu")
-            tot = torch.tensor([processed, loss, acc_las, acc_uas, acc_uas_e, steps], dtype=torch.float64, device=dev)
-            torch.distributed.all_reduce(tot, group=self.group)
+            t = torch.tensor(tot + list(more), dtype=torch.float64, device=dev)
+            torch.distributed.all_reduce(t, group=self.group)
             mx = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             torch.distributed.all_reduce(mx, op=torch.distributed.ReduceOp.MAX, group=self.group)
-            t = tot.cpu().numpy()
-            processed, loss, acc_las, acc_uas, acc_uas_e, steps = (float(t[0]), float(t[1]), float(t[2]), float(t[3]),
-                                                                   float(t[4]), int(t[5]))
-            elapsed = float(mx.item())
-        processed = max(processed, 1)
-        return (loss / processed, acc_las / processed, acc_uas / processed, acc_uas_e / processed,
-                processed / elapsed, steps)
-
-    def _pinned_decode(self, slot, t):
-        """score_epoch's page-locked fetch buffers (loss, counts): two sets
-        alternate, as _pinned's do, for the one batch in flight."""
-        pool = self.__dict__.setdefault("_pin_pool_decode", {})
-        flip = getattr(self, "_pin_flip_decode", 0)
-        buf = pool.get((slot, flip))
-        n = t.numel()
-        if buf is None or buf.numel() < n or buf.dtype != t.dtype:
-            buf = torch.empty(max(n, 1), dtype=t.dtype, pin_memory=True)
-            pool[(slot, flip)] = buf
-        if slot == 1:
-            self._pin_flip_decode = flip ^ 1
-        return buf[:n].view(t.shape)
-
-    def _fetch_batch(self, loss, feed):
-        """Queue the device -> host copies of one batch's loss and heads'
-        probabilities (page-locked buffers, one event) and keep the host arrays
-        its scoring reads; _finish_batch waits for them.  run_epoch scores a
-        batch after queueing the next one, so the host's LAS/UAS work overlaps
-        the GPU step instead of alternating with it (the reference's sess.run
-        returns every fetch before the host continues, chem_tensorflow.py:594)."""
-        ph = dict(self.placeholders)
-        dev = [loss.detach(), self.ops["computed_values"].detach(), self.ops["computed_values_edges"].detach()]
-        p = {"b": int(feed["num_graphs"]), "feed": feed, "ph": ph}
-        if dev[0].device.type != "cuda":
-            p["host"], p["event"] = [t.cpu() for t in dev], None
-            return p
-        host = [self._pinned(i, t) for i, t in enumerate(dev)]
-        for h, t in zip(host, dev):
-            h.copy_(t, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev[0].device))
-        p["host"], p["event"] = host, ev
-        return p
-
-    def _pinned(self, slot, t):
-        """A page-locked host tensor shaped like device tensor t for fetch slot
-        `slot`, from a small pool (a pinned allocation per batch cost more than
-        the copy).  Two sets alternate: run_epoch keeps one batch in flight."""
-        pool = self.__dict__.setdefault("_pin_pool", {})
-        self._pin_flip = getattr(self, "_pin_flip", 0)
-        key = (slot, self._pin_flip)
-        buf = pool.get(key)
-        n = t.numel()
-        if buf is None or buf.numel() < n or buf.dtype != t.dtype:
-            buf = torch.empty(max(n, 1), dtype=t.dtype, pin_memory=True)
-            pool[key] = buf
-        if slot == 2:
-            self._pin_flip ^= 1       # the last fetch of a batch: the next batch takes the other set
-        return buf[:n].view(t.shape)
-
-    def _finish_batch(self, p):
-        """(loss, _score_arrays(...)) of a batch queued by _fetch_batch."""
-        if p["event"] is not None:
-            p["event"].synchronize()
-        hl, hp, hpe = p["host"]
-        # (copies: the pinned buffers are reused two batches later, and run_epoch
-        # keeps the probabilities in its returned lists)
-        return float(hl.sum()), self._score_arrays(p["ph"], hp.numpy().copy(), hpe.numpy().copy())
+            t = t.cpu().numpy()
+            tot, more, elapsed = [float(x) for x in t[:5]] + [int(t[5])], t[6:], float(mx.item())
+        return (max(tot[0], 1), *tot[1:], more, elapsed)
 
     def _check_schedule_agrees(self, sched) -> None:
         """Data parallel: every rank must draw the same epoch schedule (the
@@ -1259,84 +1202,41 @@ class DenseGGNNChemModel(BtbBatching):
         slowest rank's epoch time; a training batch's loss is the global
         step's (union-batch) loss.  The per-batch lists (labels, computed
         values, ...) hold this rank's batches only."""
-        loss = 0.0
         accuracies = []
-        processed, steps = 0, 0
-        acc_las = acc_uas = acc_uas_e = 0.0
         lists = {k: [] for k in ("labels", "cv", "nv", "mask", "ids", "adj", "labels_e", "cv_e", "mask_e")}
 
+        def step(feed, all_reduce):
+            if is_training:
+                feed["out_layer_dropout_keep_prob"] = self.params["out_layer_dropout_keep_prob"]
+                loss = self.train_step(feed, all_reduce=all_reduce)
+            else:
+                loss = self._eval_forward(feed)
+            # the fetch diet: the loss and the two heads' probabilities
+            dev = [loss.detach(), self.ops["computed_values"].detach(), self.ops["computed_values_edges"].detach()]
+            p = {"feed": feed, "ph": dict(self.placeholders), "event": None}
+            if dev[0].device.type != "cuda":
+                p["host"] = [t.cpu() for t in dev]
+            else:
+                p["host"], p["event"] = self._fetch_probs.fetch(dev)
+            return p
+
         def consume(p):
-            # host side of one batch, run after the NEXT batch's step is queued
-            nonlocal loss, processed, steps, acc_las, acc_uas, acc_uas_e
-            b, feed = p["b"], p["feed"]
-            batch_loss, scored = self._finish_batch(p)
-            las, uas, uas_e, labels, cv, mask, labels_e, cv_e, mask_e = scored
-            processed += b
-            loss += batch_loss * b
+            feed, (hl, hp, hpe) = p["feed"], p["host"]
+            b, batch_loss = int(feed["num_graphs"]), float(hl.sum())
+            # (copies: the pinned buffers are reused two batches later, and the
+            # probabilities stay in the returned lists)
+            las, uas, uas_e, labels, cv, mask, labels_e, cv_e, mask_e = self._score_arrays(
+                p["ph"], hp.numpy().copy(), hpe.numpy().copy())
             accuracies.append(np.array([batch_loss] * len(self.params["task_ids"])) * b)
-            acc_las += las * b
-            acc_uas += uas * b
-            acc_uas_e += uas_e * b
-            if verbose:
-                print("Running %s, batch %i (has %i graphs). Loss so far: %.4f" % (
-                    epoch_name, steps, b, loss / processed), end="\r")
-            steps += 1
             for k, x in (("labels", labels), ("cv", cv), ("nv", int(feed["num_vertices"])), ("mask", mask),
                          ("ids", feed.get("sentences_id")), ("adj", feed.get("adjacency_matrix")),
                          ("labels_e", labels_e), ("cv_e", cv_e), ("mask_e", mask_e)):
                 lists[k].append(x)
+            return b, batch_loss, las, uas, uas_e
 
-        start = time.time()
-        pending = None
-        world = self.world_size
-        all_reduce = _dist.all_reduce_sum(self.group) if world > 1 else None
-        if world > 1 and all_reduce is None:
-            raise RuntimeError("world_size %d but torch.distributed is not initialised" % world)
-        sched = self.minibatch_schedule(data, is_training)
-        if world > 1:
-            self._check_schedule_agrees(sched)
-        it = self.make_minibatch_iterator(data, is_training, rank=self.rank, world_size=world, schedule=sched)
-        for feed in ThreadedIterator(it, max_queue_size=5):
-            if int(feed["num_graphs"]) == 0:     # no batch for this rank in the last global step
-                if is_training:
-                    self.train_step(feed, all_reduce=all_reduce)
-                continue
-            if is_training:
-                feed["out_layer_dropout_keep_prob"] = self.params["out_layer_dropout_keep_prob"]
-                batch_loss = self.train_step(feed, all_reduce=all_reduce)
-            else:
-                feed["out_layer_dropout_keep_prob"] = 1.0
-                batch_loss = None
-                if self._graph_ok(feed):
-                    with torch.no_grad():
-                        batch_loss = self._graph_step(feed, False)
-                if batch_loss is None:
-                    self.graph_stats["eager"] += 1
-                    self.feed(feed)
-                    with torch.no_grad():
-                        batch_loss = self.build_loss()
-            cur = self._fetch_batch(batch_loss, feed)
-            # one batch in flight: the host scores batch k while the GPU runs k + 1
-            if pending is not None:
-                consume(pending)
-            pending = cur
-        if pending is not None:
-            consume(pending)
-        elapsed = time.time() - start
-        acc_sum = np.sum(accuracies, axis=0) if accuracies else np.zeros(len(self.params["task_ids"]))
-        if world > 1:
-            # one reduction of the epoch's sums over the ranks (off the step loop)
-            dev = self.device if torch.distributed.get_backend(self.group) == "nccl" else torch.device("cpu")
-            tot = torch.tensor([processed, loss, acc_las, acc_uas, acc_uas_e, steps] + list(acc_sum),
-                               dtype=torch.float64, device=dev)
-            torch.distributed.all_reduce(tot, group=self.group)
-            mx = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-            torch.distributed.all_reduce(mx, op=torch.distributed.ReduceOp.MAX, group=self.group)
-            t = tot.cpu().numpy()
-            processed, loss, acc_las, acc_uas, acc_uas_e, steps = (float(t[0]), float(t[1]), float(t[2]), float(t[3]),
-                                                                   float(t[4]), int(t[5]))
-            acc_sum, elapsed = t[6:], float(mx.item())
-        processed = max(processed, 1)
+        task_sums = lambda: np.sum(accuracies, axis=0) if accuracies else np.zeros(len(self.params["task_ids"]))
+        processed, loss, acc_las, acc_uas, acc_uas_e, steps, acc_sum, elapsed = self._epoch(
+            data, is_training, step, consume, task_sums, epoch_name if verbose else None)
         accuracies = acc_sum / processed
         loss = loss / processed
         error_ratios = accuracies / self.CHEMICAL_ACCURACIES[self.params["task_ids"]]

@@ -8,6 +8,8 @@ and issues an asynchronous copy on the current stream; before the buffer is
 reused, it waits for the previous copy (an event), which has normally long
 completed.  One uploader per call site, so uploads of one batch never share a
 buffer.
+
+``PinnedFetch`` is the other direction: a batch's results, device -> host.
 """
 from __future__ import annotations
 
@@ -43,3 +45,34 @@ class Uploader:
         self._event = torch.cuda.Event()
         self._event.record(torch.cuda.current_stream(dev))
         return out
+
+
+class PinnedFetch:
+    """Device -> host fetches of a batch's small results (a loss, the heads'
+    probabilities, the decode's counts) into page-locked buffers kept from
+    batch to batch: a pinned allocation per batch cost more than the copy.
+    Two sets of buffers alternate, so the views of one fetch stay valid while
+    the next one is queued: the epoch loops keep one batch in flight."""
+
+    def __init__(self):
+        self._sets = ({}, {})
+        self._flip = 0
+
+    def fetch(self, tensors):
+        """Queue the copies of ``tensors`` (device tensors; the i-th always
+        lands in slot i's buffer) on the current stream and record one event
+        after them.  Returns (host views shaped like the tensors, event)."""
+        pool = self._sets[self._flip]
+        self._flip ^= 1              # the next fetch takes the other set
+        host = []
+        for slot, t in enumerate(tensors):
+            buf = pool.get(slot)
+            n = t.numel()
+            if buf is None or buf.numel() < n or buf.dtype != t.dtype:
+                buf = pool[slot] = torch.empty(max(n, 1), dtype=t.dtype, pin_memory=True)
+            host.append(buf[:n].view(t.shape))
+        for h, t in zip(host, tensors):
+            h.copy_(t, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(tensors[0].device))
+        return host, ev

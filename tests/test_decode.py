@@ -72,6 +72,8 @@ def test_decode_arrays_and_scores_match_the_host_scorer():
         assert pred.dtype == gold.dtype == counts.dtype == np.int32
         assert pred.shape == gold.shape == (b, v, 2) and counts.shape == (b, 5)
         with np.errstate(invalid="ignore"):
+            # (the same pred from a feed's own masks, as predict_batch takes it without closed-form masks)
+            assert (E.pred_from_masks(flat(ph), flat(pe), m, m_e) == pred).all(), trial
             _, res, tgt = E.results_reshaped_btb(args[0], args[1], args[3], v, o, e)
             _, res_e, tgt_e = E.results_reshaped_btb(args[4], args[5], args[6], v, o, e, is_edge=True)
         for g in range(b):
@@ -279,6 +281,16 @@ def test_evaluate_batch_on_device_equals_the_host_scorer():
     feed["node_mask"] = mask
     assert m._feed_n_nodes(feed) is None
     assert m.evaluate_batch(feed, on_device=True) == m.evaluate_batch(feed)
+    # ... and predict_batch decodes on the host with the feed's own masks
+    p = m.predict_batch(feed)
+    b, v, o, oe = feed["num_graphs"], feed["num_vertices"], m.params["output_size"], m.output_size_edges
+    cv, cv_e = m.ops["computed_values"].numpy(), m.ops["computed_values_edges"].numpy()
+    _, res, _ = E.results_reshaped_btb(np.zeros_like(cv), cv, mask.reshape(b, -1), v, o, oe)
+    _, res_e, _ = E.results_reshaped_btb(np.zeros_like(cv_e), cv_e, np.reshape(feed["node_mask_edges"], (b, -1)),
+                                         v, o, oe, is_edge=True)
+    for g in range(b):
+        assert E.lists_from_decoded(np.stack([p["heads"][g], p["labels"][g]], axis=1)) == (
+            E.adj_mat_to_target(res[g], is_probability=True), E.adj_mat_to_target(res_e[g], is_probability=True))
 
 
 def test_score_epoch_equals_run_epoch_on_a_cpu_device():
@@ -288,3 +300,6 @@ def test_score_epoch_equals_run_epoch_on_a_cpu_device():
     got = m.score_epoch(data)
     assert got[:4] == (ref[0], ref[5], ref[6], ref[16]) and got[5] == ref[4]
     assert m.decode_stats["graphs"] == 20
+    # the shared epoch loop's progress line changes no value
+    loud = m.run_epoch("valid", data, False, verbose=True)
+    assert (loud[0], loud[4], loud[5], loud[6], loud[16]) == (ref[0], ref[4], ref[5], ref[6], ref[16])
