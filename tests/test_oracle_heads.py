@@ -117,6 +117,106 @@ def test_embed_backward_is_the_adjoint(keep):
     assert abs(sq[1] - np.sum(g[:, :, 3:5] ** 2)) < 1e-9
 
 
+@pytest.mark.parametrize("keep", [1.0, 0.6])
+def test_embed_out_of_range_ids_contribute_nothing(keep):
+    """Ids outside [0, rows) against a hand-written loop on a tiny case: a zero
+    row forward; no table row and no share of the squared norm backward.  With
+    every id in range the results are those of the plain fancy-index form."""
+    rng = np.random.default_rng(4)
+    loc, pos = rng.normal(size=(5, 3)), rng.normal(size=(4, 2))
+    segs = [(loc, 0), (pos, 1), (loc, 2)]
+    hd, b, v = 10, 2, 3
+    wi = np.array([[[0, 1, 4], [-1, 3, 5], [2, 4, 1 << 30]],
+                   [[4, -7, 0], [5, 0, -1], [3, 2, 2]]])
+    G = rng.normal(size=(b, v, hd))
+    keepf = np.float64(np.float32(keep))
+    mask = O.emb_keep_mask(b * v, hd, keep, 11).reshape(b, v, hd) if keep < 1 else np.ones((b, v, hd), bool)
+    h0 = np.zeros((b, v, hd))
+    dts = [np.zeros_like(t) for t, _ in segs]
+    sq = [0.0] * len(segs)
+    for g in range(b):
+        for i in range(v):
+            off = 0
+            for s, (t, col) in enumerate(segs):
+                idx = wi[g, i, col]
+                for k in range(t.shape[1]):
+                    if 0 <= idx < t.shape[0] and mask[g, i, off + k]:
+                        h0[g, i, off + k] = t[idx, k] / keepf
+                    gv = G[g, i, off + k] / keepf if mask[g, i, off + k] else 0.0
+                    if 0 <= idx < t.shape[0]:
+                        dts[s][idx, k] += gv
+                        sq[s] += gv * gv
+                off += t.shape[1]
+    np.testing.assert_allclose(O.embed_forward(segs, wi, hd, keep, 11), h0, rtol=0, atol=1e-15)
+    rd, rsq = O.embed_backward(segs, wi, hd, G, keep, 11)
+    for a, r in zip(rd, dts):
+        np.testing.assert_allclose(a, r, rtol=0, atol=1e-14)
+    np.testing.assert_allclose(rsq, sq, rtol=1e-13)
+    # every id in range: the plain form (table[ids], np.add.at over every row), bit for bit
+    wi_ok = rng.integers(0, 4, size=(b, v, 3))
+    plain = np.concatenate([np.asarray(t)[wi_ok[:, :, c]] for t, c in segs] + [np.zeros((b, v, 2))], axis=2)
+    plain = np.where(mask, plain / keepf, 0.0) if keep < 1 else plain
+    assert np.array_equal(O.embed_forward(segs, wi_ok, hd, keep, 11), plain)
+    rd, rsq = O.embed_backward(segs, wi_ok, hd, G, keep, 11)
+    gm = np.where(mask, G / keepf, 0.0) if keep < 1 else G
+    off = 0
+    for s, (t, c) in enumerate(segs):
+        w = t.shape[1]
+        dt = np.zeros(t.shape)
+        np.add.at(dt, wi_ok[:, :, c].reshape(-1), gm[:, :, off:off + w].reshape(-1, w))
+        assert np.array_equal(rd[s], dt)
+        assert rsq[s] == float(np.sum(gm[:, :, off:off + w].reshape(-1, w) ** 2))
+        off += w
+
+
+def test_adam_step_sqnorm_override():
+    """adam_step(sqnorms=...): the override replaces ||g||^2 in clip_by_norm,
+    times grad_scale^2; None entries and sqnorms=None leave the step as it was.
+    Against a hand-written loop on a tiny case, overrides on both sides of the
+    clip."""
+    lr, b1, b2, eps, clip, gs = 0.003, 0.9, 0.999, 1e-8, 1.0, 0.5
+    p0 = [np.array([0.1, -0.2, 0.3]), np.array([0.05]), np.array([[0.2, -0.1], [0.4, 0.3]])]
+    g = [np.array([3.0, -4.0, 1.0]), np.array([0.25]), np.array([[0.5, -0.5], [0.25, 1.0]])]
+    sqn = [100.0, None, 0.01]          # 0.5 * 10 > clip;  own norm;  0.5 * 0.1 < clip (no clipping)
+    ref = [x.copy() for x in p0]
+    m = [np.zeros_like(x) for x in p0]
+    v = [np.zeros_like(x) for x in p0]
+    hand_p = [x.copy() for x in p0]
+    hand_m = [np.zeros_like(x) for x in p0]
+    hand_v = [np.zeros_like(x) for x in p0]
+    for t in (1, 2):
+        O.adam_step(ref, g, m, v, t, lr=lr, beta1=b1, beta2=b2, eps=eps, clip_norm=clip, grad_scale=gs, sqnorms=sqn)
+        lr_t = lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
+        for i in range(3):
+            flat_g = (g[i] * gs).reshape(-1)
+            norm = np.sqrt(sqn[i] * gs * gs) if sqn[i] is not None else np.sqrt(sum(x * x for x in flat_g))
+            for j in range(flat_g.size):
+                gc = flat_g[j] * clip / max(norm, clip)
+                hm, hv, hp = hand_m[i].reshape(-1), hand_v[i].reshape(-1), hand_p[i].reshape(-1)
+                hm[j] = b1 * hm[j] + (1 - b1) * gc
+                hv[j] = b2 * hv[j] + (1 - b2) * gc * gc
+                hp[j] -= lr_t * hm[j] / (np.sqrt(hv[j]) + eps)
+    for a, r in zip(ref, hand_p):
+        np.testing.assert_allclose(a, r, rtol=1e-13, atol=0)
+    # no override: unchanged results, with sqnorms absent or all None
+    outs = []
+    for kw in ({}, {"sqnorms": None}, {"sqnorms": [None] * 3}):
+        pp = [x.copy() for x in p0]
+        mm = [np.zeros_like(x) for x in p0]
+        vv = [np.zeros_like(x) for x in p0]
+        O.adam_step(pp, g, mm, vv, 1, lr=lr, clip_norm=clip, grad_scale=gs, **kw)
+        outs.append(pp)
+        for i in range(3):
+            gc = O.clip_by_norm(g[i] * gs, clip)
+            np.testing.assert_allclose(pp[i], p0[i] - lr * np.sqrt(1 - b2) / (1 - b1) * ((1 - b1) * gc)
+                                       / (np.sqrt((1 - b2) * gc * gc) + eps), rtol=1e-14, atol=0)
+    for o in outs[1:]:
+        for a, r in zip(o, outs[0]):
+            assert np.array_equal(a, r)
+    # tensor 0's own norm (0.5 * sqrt(26)) and its override (0.5 * 10) clip differently
+    assert not np.allclose(O.clip_by_norm(g[0] * gs, clip), O.clip_by_norm(g[0] * gs, clip, sqn[0] * gs * gs))
+
+
 def test_dropout_masks_of_the_callers_are_independent_streams():
     e = O.emb_keep_mask(64, 32, 0.5, 7)
     h = O.head_keep_mask(64, 32, 0, 0.5, 7)
