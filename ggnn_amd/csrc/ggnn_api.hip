@@ -21,6 +21,7 @@
 #include "k_wgrad.h"
 #include "k_head.h"
 #include "k_decode.h"
+#include "k_tree.h"
 #include "k_gemm.h"
 #include "k_gemm_ring.h"
 #include "k_generic.h"
@@ -1751,6 +1752,35 @@ int ggnn_heads_decode(const ggnn_dims* d, const float* probs_head, int32_t o, co
   if (std::max(o, oe) <= 256) HDEC(4);
   else HDEC(HEAD_MAXO / 64);
 #undef HDEC
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+
+// the tree post-pass on ggnn_heads_decode's pred (k_tree.h); booked under the
+// heads kind
+static_assert(GGNN_TREE_MAXV == TREE_MAXV && GGNN_TREE_FORBIDDEN == TREE_FORBIDDEN, "tree decode constants");
+size_t ggnn_tree_decode_workspace_bytes(int32_t, int32_t) { return 0; }
+int ggnn_tree_decode(const ggnn_dims* d, const int32_t* scores, int32_t o, const int32_t* n_nodes,
+                     int32_t single_root, int32_t* pred, const int32_t* gold, int32_t* counts, int32_t* status,
+                     void* /*workspace*/, size_t /*workspace_bytes*/, ggnn_stream_t stream) {
+  if (!d) return fail(GGNN_EINVAL, "tree_decode: dims is NULL");
+  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "tree_decode: b, v must be >= 1");
+  if (o < 1 || o > HEAD_MAXO)
+    return fail(GGNN_EINVAL, "tree_decode: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
+                                 std::to_string(o) + ")");
+  if (d->v > o) return fail(GGNN_EINVAL, "tree_decode: v " + std::to_string(d->v) + " > o " + std::to_string(o));
+  if (d->v > GGNN_TREE_MAXV)
+    return fail(GGNN_EINVAL, "tree_decode: v " + std::to_string(d->v) + " > GGNN_TREE_MAXV " +
+                                 std::to_string(GGNN_TREE_MAXV));
+  if (single_root != 0 && single_root != 1) return fail(GGNN_EINVAL, "tree_decode: single_root must be 0 or 1");
+  if (!scores || !n_nodes || !pred || !status) return fail(GGNN_EINVAL, "tree_decode: NULL pointer");
+  if ((gold == nullptr) != (counts == nullptr))
+    return fail(GGNN_EINVAL, "tree_decode: gold and counts must be given together (one is NULL)");
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_tree_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
+                     (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
+                     (int*)status);
   LAUNCHCHK();
   return GGNN_OK;
 }

@@ -301,3 +301,207 @@ def _batch_las_uas_lists(res, tgt, res_e, tgt_e):
         acc_uas += uas
         acc_uas_e += uas_e
     return acc_las / b, acc_uas / b, acc_uas_e / b
+
+
+# ------------------------------------------------- tree-constrained decoding
+# Host forms of ``ggnn_tree_decode`` (include/ggnn.h): the maximum spanning
+# arborescence of the head scores (Chu-Liu/Edmonds), exact integer arithmetic.
+TREE_FORBIDDEN = -2 ** 31      # GGNN_TREE_FORBIDDEN
+TREE_MAXV = 256                # GGNN_TREE_MAXV
+TREE_LOG2_FLOOR = 150          # |log2| of the smallest positive float32 is 149
+# a ROOT arc costs this much more under single_root: more than any difference
+# of two trees' totals (2 * 255 * 2^31 < 2^40), far inside int64
+_ROOT_PENALTY = 2 ** 42
+
+
+def tree_score_shift(v):
+    """k of tree_scores: the largest k <= 16 with 150 * 2^k * v * (v + 1) <=
+    2^30 (the exactness contract of ggnn_tree_decode; 7 at v = 198, 12 at 40)."""
+    k = 16
+    while k > 0 and TREE_LOG2_FLOOR * int(v) * (int(v) + 1) * 2 ** k > 2 ** 30:
+        k -= 1
+    return k
+
+
+def tree_scores(probs_head, n_nodes, v):
+    """Integer arc scores of a batch for the tree decode: probs_head [b, v, o]
+    -> int32 [b, v, o] with rint(log2(p) * 2^k), clamped below at -150 * 2^k,
+    and TREE_FORBIDDEN where p <= 0 or p is NaN / +-inf, the row or column is
+    >= n, the row is 0 or the arc is a self-loop.  The sum of the scores of a
+    tree is the log of the product of its head probabilities at 2^-k bits."""
+    p = np.asarray(probs_head, np.float32)
+    if p.ndim != 3 or p.shape[1] != int(v):
+        raise ValueError("probs_head [b, %d, o] expected, got %s" % (int(v), p.shape))
+    b, _, o = p.shape
+    n = np.asarray(n_nodes).astype(np.int64).reshape(-1, 1, 1)
+    k = tree_score_shift(v)
+    i = np.arange(int(v)).reshape(1, -1, 1)
+    j = np.arange(o).reshape(1, 1, -1)
+    ok = np.isfinite(p) & (p > 0) & (i < n) & (j < n) & (i != 0) & (i != j)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.rint(np.log2(np.where(ok, p, 1).astype(np.float64)) * float(2 ** k))
+    q = np.maximum(q, -TREE_LOG2_FLOOR * 2 ** k)
+    return np.where(ok, q, TREE_FORBIDDEN).astype(np.int32)
+
+
+def _arc_allowed(scores, n, i, j):
+    return 1 <= i < n and 0 <= j < n and j != i and int(scores[i][j]) != TREE_FORBIDDEN
+
+
+def is_tree(heads, n, single_root, scores=None):
+    """heads[i] for the words i in 1..n-1 (heads[0] is ignored): every head
+    lies in 0..n-1, is not the word itself (and is an allowed arc of
+    ``scores`` when given), following the heads from any word reaches node 0,
+    and with single_root exactly one word has head 0."""
+    n = int(n)
+    h = [int(x) for x in heads[:n]]
+    for i in range(1, n):
+        if not (0 <= h[i] < n) or h[i] == i:
+            return False
+        if scores is not None and int(scores[i][h[i]]) == TREE_FORBIDDEN:
+            return False
+    for i in range(1, n):
+        x = i
+        for _ in range(n):
+            if x == 0:
+                break
+            x = h[x]
+        if x != 0:
+            return False
+    return not single_root or n < 2 or sum(1 for i in range(1, n) if h[i] == 0) == 1
+
+
+def tree_total(scores, heads, n):
+    """The sum of scores[i][heads[i]] over the words 1..n-1 (a Python int)."""
+    return sum(int(scores[i][int(heads[i])]) for i in range(1, int(n)))
+
+
+def _max_arborescence(s, n, single_root):
+    """Chu-Liu/Edmonds on one graph, in the kernel's formulation: a supernode
+    label and an accumulated offset per word give the adjusted score of an arc
+    from the original scores; every round contracts all cycles of the
+    supernodes' best incoming arcs; the contraction forest is expanded at the
+    end.  Returns (heads or None when no tree exists, nesting levels)."""
+    none = -2 ** 62
+    s = np.asarray(s)[:n, :n].astype(np.int64)
+    key = s.copy()
+    if single_root:
+        key[:, 0] -= _ROOT_PENALTY
+    key[s == TREE_FORBIDDEN] = none
+    key[0, :] = none
+    key[np.arange(n), np.arange(n)] = none
+    label = np.arange(n)            # word -> live node of the contraction forest
+    off = np.zeros(n, np.int64)
+    tpar = [-1] * (2 * n)           # forest parent; ids < n: the words themselves
+    depth = [0] * (2 * n)
+    in_u, in_i, best = [0] * (2 * n), [0] * (2 * n), [0] * (2 * n)
+    nid, first_new = n, 1
+    levels = 0
+    done = False
+    for _ in range(n):
+        for x in range(first_new, nid):          # the nodes new in this round
+            members = np.flatnonzero(label == x)
+            vals = np.where((label != x)[None, :] & (key[members] != none), key[members] - off[members, None], none)
+            k = int(vals.argmax())               # first word, then first column
+            w, j = divmod(k, n)
+            if vals[w, j] == none:
+                return None, levels
+            best[x], in_u[x], in_i[x] = int(vals[w, j]), j, int(members[w])
+        live = sorted(set(int(x) for x in label[1:]))
+        par = {x: int(label[in_u[x]]) for x in live}
+        par[0] = 0
+        on_cycle = {}
+        state = {0: 2}                           # 1 = on the current walk, 2 = settled
+        for x in live:
+            walk, y = [], x
+            while y not in state:
+                state[y] = 1
+                walk.append(y)
+                y = par[y]
+            if state[y] == 1:
+                cyc = walk[walk.index(y):]
+                for z in cyc:
+                    on_cycle[z] = min(cyc)
+            for z in walk:
+                state[z] = 2
+        if not on_cycle:
+            done = True
+            break
+        first_new = nid
+        new_of = {}
+        for lead in sorted(set(on_cycle.values())):
+            new_of[lead] = nid
+            nid += 1
+        for x, lead in on_cycle.items():
+            tpar[x] = new_of[lead]
+            depth[new_of[lead]] = max(depth[new_of[lead]], depth[x] + 1)
+            levels = max(levels, depth[new_of[lead]])
+        for i in range(1, n):
+            x = int(label[i])
+            if x in on_cycle:
+                off[i] += best[x]
+                label[i] = new_of[on_cycle[x]]
+    if not done:
+        return None, levels
+    heads = [-1] * n
+    entered = [False] * (2 * n)
+    for x in range(nid - 1, 0, -1):
+        if entered[x]:
+            continue
+        heads[in_i[x]] = in_u[x]
+        y = in_i[x]
+        while y != x:
+            entered[y] = True
+            y = tpar[y]
+    if single_root and sum(1 for i in range(1, n) if heads[i] == 0) != 1:
+        return None, levels
+    return heads, levels
+
+
+def tree_decode_arrays(scores, n_nodes, pred, single_root=True, gold=None, counts=None, levels=None):
+    """The host form of ``ggnn_tree_decode`` (include/ggnn.h).  scores int32
+    [b, v, o], n_nodes [b], pred int32 [b, v, 2] (decode_arrays'), gold
+    [b, v, 2] and counts [b, 5] together or both None.  Returns (pred, counts,
+    status): copies with every graph whose heads pred[g, 1:n, 0] are not a tree
+    over the allowed arcs (status 1) given a tree of maximum total score and
+    its las / uas counts recounted; status 0 = already a tree, 2 = no tree
+    exists; those graphs are returned as passed in.  ``levels``: a list that
+    receives per graph the nesting depth of the contractions it needed."""
+    s = np.asarray(scores)
+    if s.ndim != 3 or s.dtype != np.int32:
+        raise ValueError("scores must be int32 [b, v, o]")
+    b, v, o = s.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("tree decode needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    pred = np.array(pred, np.int32)
+    if pred.shape != (b, v, 2):
+        raise ValueError("pred must be [%d, %d, 2]" % (b, v))
+    if (gold is None) != (counts is None):
+        raise ValueError("gold and counts are given together")
+    if counts is not None:
+        counts = np.array(counts, np.int32)
+        gold = np.asarray(gold)
+    nn = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
+    if nn.shape[0] != b:
+        raise ValueError("n_nodes: %d values for %d graphs" % (nn.shape[0], b))
+    status = np.zeros(b, np.int32)
+    if levels is not None:
+        del levels[:]
+    for g in range(b):
+        n = int(nn[g])
+        lv = 0
+        if n >= 2 and not is_tree(pred[g, :, 0], n, single_root, s[g]):
+            heads, lv = _max_arborescence(s[g], n, single_root)
+            if heads is None:
+                status[g] = 2
+            else:
+                status[g] = 1
+                pred[g, 1:n, 0] = heads[1:]
+                if counts is not None:
+                    has = gold[g, 1:, 0] >= 0
+                    hit_h = has & (pred[g, 1:, 0] == gold[g, 1:, 0])
+                    counts[g, 1] = int((hit_h & (pred[g, 1:, 1] == gold[g, 1:, 1])).sum())
+                    counts[g, 2] = int(hit_h.sum())
+        if levels is not None:
+            levels.append(lv)
+    return pred, counts, status

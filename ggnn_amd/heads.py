@@ -24,6 +24,7 @@ from .upload import Uploader
 from . import _lib
 
 SMALL_NUMBER = 1e-7   # utils.py
+TREE_LOG2_FLOOR = 150  # tree_scores: |log2| of the smallest positive float32 is 149
 
 
 class EmbedSegment(ctypes.Structure):          # include/ggnn.h: ggnn_embed_segment
@@ -171,6 +172,7 @@ class OutputHeads:
         self.hidden = int(hidden)
         self._lib = _lib.load()
         self._ws = None
+        self._tree_ws = None   # ggnn_tree_decode's workspace (the kernel asks for none today)
         self._saved = None
 
     def _table(self, heads, labels, probs, dws=None, dbs=None):
@@ -272,6 +274,74 @@ class OutputHeads:
                                                _ptr(n_nodes), _ptr(pred), _ptr(gold), _ptr(counts), _stream()),
                    "ggnn_heads_decode")
         return pred, gold, counts
+
+    def tree_decode(self, scores, n_nodes, pred, gold=None, counts=None, single_root=True):
+        """The tree post-pass on ``decode``'s pred, on the same stream
+        (ggnn_tree_decode).  scores: int32 [b, v, o] (``tree_scores``);
+        n_nodes: int32 [b]; pred: int32 [b, v, 2], updated in place; gold
+        [b, v, 2] and counts [b, 5] (decode's) together or both None: a
+        repaired graph's las / uas counts are recounted in place.  Returns
+        status int32 [b]: 0 = pred's heads already were a tree, 1 = replaced
+        by the maximum spanning tree of the scores, 2 = no tree exists (the
+        graph is left as it was)."""
+        if scores.dim() != 3 or scores.dtype != torch.int32 or scores.device.type != "cuda":
+            raise ValueError("scores must be an int32 [b, v, o] tensor on the GPU")
+        if not scores.is_contiguous():
+            raise ValueError("scores must be contiguous")
+        b, v, o = scores.shape
+        dev = scores.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("tree_decode needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
+        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
+            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
+        if (gold is None) != (counts is None):
+            raise ValueError("gold and counts are given together")
+        for t, name, shape in ((pred, "pred", (b, v, 2)), (gold, "gold", (b, v, 2)),
+                               (counts, "counts", (b, _lib.DECODE_COUNTS))):
+            if t is not None and (t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape
+                                  or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous int32 %s tensor on %s" % (name, list(shape), dev))
+        need = int(self._lib.ggnn_tree_decode_workspace_bytes(b, v))
+        if need and (self._tree_ws is None or self._tree_ws.numel() < need or self._tree_ws.device != dev):
+            self._tree_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_tree_decode(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes), int(bool(single_root)),
+                                              _ptr(pred), _ptr(gold), _ptr(counts), _ptr(status),
+                                              _ptr(self._tree_ws) if need else None, need, _stream()),
+                   "ggnn_tree_decode")
+        return status
+
+
+def tree_score_shift(v):
+    """k of tree_scores: the largest k <= 16 with 150 * 2^k * v * (v + 1) <=
+    2^30 (evaluation.tree_score_shift; ggnn_tree_decode's exactness contract)."""
+    k = 16
+    while k > 0 and TREE_LOG2_FLOOR * int(v) * (int(v) + 1) * 2 ** k > 2 ** 30:
+        k -= 1
+    return k
+
+
+def tree_scores(probs_head, n_nodes, v):
+    """Integer arc scores for ``OutputHeads.tree_decode`` on the tensor's
+    device (plain torch, evaluation.tree_scores is the numpy form):
+    probs_head float32 [b, v, o], n_nodes [b] -> int32 [b, v, o] with
+    rint(log2(p) * 2^k) clamped below at -150 * 2^k, and GGNN_TREE_FORBIDDEN
+    where p <= 0 or p is NaN / +-inf, the row or column is >= n, the row is 0
+    or the arc is a self-loop."""
+    p = probs_head
+    if p.dim() != 3 or p.shape[1] != int(v):
+        raise ValueError("probs_head [b, %d, o] expected, got %s" % (int(v), tuple(p.shape)))
+    dev = p.device
+    o = p.shape[2]
+    n = torch.as_tensor(n_nodes, device=dev).to(torch.int64).reshape(-1, 1, 1)
+    k = tree_score_shift(v)
+    i = torch.arange(int(v), device=dev).reshape(1, -1, 1)
+    j = torch.arange(o, device=dev).reshape(1, 1, -1)
+    ok = torch.isfinite(p) & (p > 0) & (i < n) & (j < n) & (i != 0) & (i != j)
+    q = torch.round(torch.log2(torch.where(ok, p, torch.ones_like(p)).to(torch.float64)) * float(2 ** k))
+    q = torch.clamp(q, min=float(-TREE_LOG2_FLOOR * 2 ** k))
+    return torch.where(ok, q, torch.full_like(q, float(_lib.TREE_FORBIDDEN))).to(torch.int32).contiguous()
 
 
 def _decode_input(t, name):

@@ -28,7 +28,9 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
 * not in the reference: ``predict_batch`` / ``parse`` (the predicted tree of a
   batch / of raw sentences) and ``evaluate_batch(on_device=True)`` /
   ``score_epoch`` (the scores from per-graph counts), decoded on the device by
-  ``ggnn_heads_decode`` (``csrc/k_decode.h``)
+  ``ggnn_heads_decode`` (``csrc/k_decode.h``); with ``tree=True`` the heads
+  of a graph that is not a dependency tree are replaced by the maximum
+  spanning tree of the head scores (``ggnn_tree_decode``, ``csrc/k_tree.h``)
 
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
@@ -60,7 +62,8 @@ from .batching import BtbBatching, ThreadedIterator
 from .dist import FlatTrainBuffer
 from .engine import PropagationEngine
 from .graphs import CapturedStep, PinnedRing, StepLayout, edge_arrays
-from .heads import SMALL_NUMBER, EmbedFunction, EmbeddingFrontEnd, HeadsFunction, OutputHeads, word_inputs_tensor
+from .heads import (SMALL_NUMBER, EmbedFunction, EmbeddingFrontEnd, HeadsFunction, OutputHeads, tree_scores,
+                    word_inputs_tensor)
 from .optim import ClipAdam
 from .upload import PinnedFetch, Uploader
 
@@ -247,7 +250,8 @@ class DenseGGNNChemModel(BtbBatching):
         # the epoch loops' device -> host fetches: run_epoch's (loss, both
         # heads' probabilities) and score_epoch's (loss, decode counts)
         self._fetch_probs, self._fetch_counts = PinnedFetch(), PinnedFetch()
-        self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0}
+        self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0, "repaired_graphs": 0,
+                             "infeasible_graphs": 0}
         self._flat = None
         self._rows = None          # the word segment's lookup rows / ids (sparse data-parallel reduction)
         # hipGraph-captured steps by batch shape (graphs.py), least recently
@@ -857,14 +861,19 @@ class DenseGGNNChemModel(BtbBatching):
 
     get_las_uas = staticmethod(_eval.get_las_uas)  # chem_tensorflow_dense.py:1304-1319
 
-    def evaluate_batch(self, feed_dict=None, on_device=False):
+    def evaluate_batch(self, feed_dict=None, on_device=False, tree=False, single_root=True):
         """(LAS, UAS, label accuracy) of one batch from the heads' probabilities
         (``humanize_batch_results_btb``, chem_tensorflow_dense.py:1160-1215):
         runs the forward + heads (no dropout) and scores on the host.
         on_device: the same three floats from the decode's per-graph counts
-        (ggnn_heads_decode; only [b, 5] int32 leave the device)."""
+        (ggnn_heads_decode; only [b, 5] int32 leave the device).  tree (with
+        on_device): the heads of every graph that is not a tree are replaced by
+        the maximum spanning tree before the counts are read (ggnn_tree_decode,
+        as predict_batch(tree=True) returns them)."""
+        if tree and not on_device:
+            raise ValueError("evaluate_batch: tree=True needs on_device=True")
         if on_device:
-            r = self._decode_forward(feed_dict, True)
+            r = self._decode_forward(feed_dict, True, tree, single_root)
             ph, b, v = r["ph"], r["b"], r["v"]
             o, oe = self.params["output_size"], self.output_size_edges
 
@@ -949,18 +958,22 @@ class DenseGGNNChemModel(BtbBatching):
                 loss = self.build_loss()
         return loss
 
-    def _decode_forward(self, feed_dict, with_gold):
+    def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True):
         """_eval_forward of a feed (default: the staged one) followed by the
         decode launch on the same stream.  Returns a dict: loss (scalar
         tensor), ph (the staged placeholders), b, v, n_nodes (host int32 [b],
         None: masks not in closed form) and pred / gold / counts -- int32
         device tensors, numpy arrays on a CPU device (decode_arrays), None
-        without n_nodes."""
+        without n_nodes.  tree: the tree post-pass follows the decode eagerly
+        on the same stream (never inside a captured step) and 'tree_status'
+        [b] joins the dict; a graph with regular == 0 is not passed to it
+        (node count 0) and gets status 2."""
         loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
         ph = dict(self.placeholders)
         b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
         o, oe = self.params["output_size"], self.output_size_edges
-        r = {"loss": loss.detach(), "ph": ph, "b": b, "v": v, "pred": None, "gold": None, "counts": None}
+        r = {"loss": loss.detach(), "ph": ph, "b": b, "v": v, "pred": None, "gold": None, "counts": None,
+             "tree_status": None}
         n = r["n_nodes"] = self._feed_n_nodes(ph)
         if n is None:
             return r
@@ -972,9 +985,24 @@ class DenseGGNNChemModel(BtbBatching):
                 y = np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o)
                 y_e = np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)
             r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(probs.numpy(), probs_e.numpy(), n, y, y_e)
+            if tree:
+                regular = r["counts"][:, 4] == 1
+                pred, counts, status = _eval.tree_decode_arrays(
+                    _eval.tree_scores(probs.numpy(), n, v), np.where(regular, n, 0), r["pred"], single_root,
+                    r["gold"], r["counts"] if with_gold else None)
+                r["pred"], r["tree_status"] = pred, np.where(regular, status, 2).astype(np.int32)
+                if with_gold:
+                    r["counts"] = counts
             return r
+        n_dev = self._up_nodes(n, self.device)
         r["pred"], r["gold"], r["counts"] = self._decode_heads().decode(
-            [probs, probs_e], self._up_nodes(n, self.device), self._last_labels if with_gold else None)
+            [probs, probs_e], n_dev, self._last_labels if with_gold else None)
+        if tree:
+            regular = r["counts"][:, 4] == 1
+            status = self._decode_heads().tree_decode(
+                tree_scores(probs, n_dev, v), (n_dev * regular).to(torch.int32), r["pred"], r["gold"],
+                r["counts"] if with_gold else None, single_root)
+            r["tree_status"] = torch.where(regular, status, torch.full_like(status, 2))
         return r
 
     def _host_pred(self, ph, b, v):
@@ -986,14 +1014,20 @@ class DenseGGNNChemModel(BtbBatching):
                                      np.asarray(ph["node_mask"], np.float32).reshape(b, v, o),
                                      np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
 
-    def predict_batch(self, feed_dict=None):
+    def predict_batch(self, feed_dict=None, tree=False, single_root=True):
         """The predicted tree of every graph of a batch: {'heads': [b, v],
         'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
         arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
         prediction: node 0, padding, an all-zero row), 'n_nodes': [b],
-        'sentences_id'}.  Runs the dropout-free forward and decodes on the
-        device; 2 * b * v int32 come back instead of both probability arrays."""
-        r = self._decode_forward(feed_dict, False)
+        'sentences_id', 'tree_status'}.  Runs the dropout-free forward and
+        decodes on the device; 2 * b * v int32 come back instead of both
+        probability arrays.  tree: 'heads' of a graph whose arg-max heads are
+        not a dependency tree (single_root: with one ROOT child) hold the
+        maximum spanning tree of the head scores instead (ggnn_tree_decode on
+        tree_scores of the head probabilities) and 'tree_status' [b] int32
+        says 0 = was a tree, 1 = repaired, 2 = no tree exists / not attempted
+        (left as the arg-max); None without tree."""
+        r = self._decode_forward(feed_dict, False, tree, single_root)
         ph, b, v = r["ph"], r["b"], r["v"]
         pred = r["pred"]
         if pred is None:
@@ -1004,16 +1038,23 @@ class DenseGGNNChemModel(BtbBatching):
             n = r["n_nodes"]
             if isinstance(pred, torch.Tensor):
                 pred = pred.cpu().numpy()
+        status = r["tree_status"]
+        if tree and status is None:          # masks not in closed form: the repair is not attempted
+            status = np.full(b, 2, np.int32)
+        elif isinstance(status, torch.Tensor):
+            status = status.cpu().numpy()
         return {"heads": np.ascontiguousarray(pred[:, :, 0]), "labels": np.ascontiguousarray(pred[:, :, 1]),
-                "n_nodes": n, "sentences_id": ph.get("sentences_id")}
+                "n_nodes": n, "sentences_id": ph.get("sentences_id"), "tree_status": status}
 
-    def parse(self, raw_data):
+    def parse(self, raw_data, tree=False, single_root=True):
         """Parse raw btb sentences (the dicts process_raw_graphs accepts;
         'targets' may be absent): one entry per input sentence, in input
         order, in the JSON's own 'targets' form [[head, label], ...] for nodes
         1..n-1 with the label one-based -- what adj_mat_to_target(...,
         is_probability=True) + merge_head_and_edge_graph give for the sentence.
-        A sentence process_raw_graphs drops (empty graph) yields []."""
+        A sentence process_raw_graphs drops (empty graph) yields [].  tree: as
+        predict_batch(tree=True): every sentence for which a dependency tree
+        exists comes back as one."""
         raw = []
         for k, d in enumerate(raw_data):
             c = dict(d)
@@ -1023,14 +1064,14 @@ class DenseGGNNChemModel(BtbBatching):
         out = [[] for _ in raw]
         data = self.process_raw_graphs(raw, False)
         for feed in self.make_minibatch_iterator(data, False):
-            p = self.predict_batch(feed)
+            p = self.predict_batch(feed, tree, single_root)
             for k, heads, labels in zip(p["sentences_id"], p["heads"], p["labels"]):
                 rg_h = [[int(x), 1] for x in heads[1:] if x >= 0]
                 rg_e = [[0, int(x) + 1] for x in labels[1:] if x >= 0]
                 out[k] = _eval.merge_head_and_edge_graph(rg_h, rg_e)
         return out
 
-    def score_epoch(self, data):
+    def score_epoch(self, data, tree=False, single_root=True):
         """The validation pass of run_epoch with the scoring on the device:
         per batch only the loss and the decode's counts [b, 5] are fetched
         (pred / gold too for a batch with an irregular graph, scored through
@@ -1038,11 +1079,16 @@ class DenseGGNNChemModel(BtbBatching):
         masks are not in closed form).  One batch in flight and the sums over
         the ranks as in run_epoch.  Returns (loss, las, uas, label_acc,
         instances_per_sec, steps) -- run_epoch's values.  ``decode_stats``
-        holds the pass's graphs, host-fallback graphs and fetched bytes."""
-        stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0}
+        holds the pass's graphs, host-fallback graphs and fetched bytes.  tree:
+        the scores are those of the tree-constrained heads (ggnn_tree_decode
+        after the decode, its status [b] fetched beside the counts);
+        ``decode_stats`` counts the repaired graphs and those without a tree
+        (a graph on the host fallback is scored from its arg-max lists)."""
+        stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0, "repaired_graphs": 0,
+                                     "infeasible_graphs": 0}
 
         def step(feed, all_reduce):
-            r = self._decode_forward(feed, True)
+            r = self._decode_forward(feed, True, tree, single_root)
             r["event"] = None
             if r["counts"] is None:          # the host scorer decides: fetch what it reads
                 r["scored"] = self._score_batch()[:3]
@@ -1051,8 +1097,12 @@ class DenseGGNNChemModel(BtbBatching):
                 stats["fallback_graphs"] += r["b"]
             elif isinstance(r["counts"], np.ndarray):   # a CPU device: decode_arrays' counts
                 r["host"] = [r["loss"].reshape(1), torch.from_numpy(r["counts"])]
+                if tree:
+                    r["host"].append(torch.from_numpy(r["tree_status"]))
             else:
                 dev = [r["loss"].reshape(1), r["counts"]]
+                if tree:
+                    dev.append(r["tree_status"])
                 r["host"], r["event"] = self._fetch_counts.fetch(dev)
                 stats["d2h_bytes"] += sum(t.numel() * t.element_size() for t in dev)
             return r
@@ -1061,7 +1111,13 @@ class DenseGGNNChemModel(BtbBatching):
             batch_loss = float(r["host"][0].sum())
             if r["counts"] is None:
                 scores = r["scored"]
+                if tree:
+                    stats["infeasible_graphs"] += r["b"]
             else:
+                if tree:
+                    status = r["host"][2].numpy()
+                    stats["repaired_graphs"] += int((status == 1).sum())
+                    stats["infeasible_graphs"] += int((status == 2).sum())
                 lists = {}
 
                 def fallback(i):

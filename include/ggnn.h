@@ -410,6 +410,53 @@ int ggnn_heads_decode(const ggnn_dims* d, /* b, v used */
                       int32_t* counts,         /* device [b][GGNN_DECODE_COUNTS] out */
                       ggnn_stream_t stream);
 
+/* Tree-constrained decoding: a post-pass on ggnn_heads_decode's pred, on the
+ * same stream.  scores are integer arc scores (heads.py tree_scores builds
+ * them from the head probabilities).  For graph g with n = n_nodes[g] clamped
+ * to [0, min(v, o)]:
+ *   allowed arc   word i takes head j: 1 <= i < n, 0 <= j < n, j != i and
+ *                 scores[g][i][j] != GGNN_TREE_FORBIDDEN; rows and columns >= n
+ *                 are ignored whatever they hold.
+ *   tree          every word 1..n-1 has one allowed head and following the
+ *                 heads from any word reaches node 0; with single_root exactly
+ *                 one word has head 0.
+ *   status[g] = 0 pred[g][1..n-1][0] as passed in is a tree (or n < 2): nothing
+ *                 of the graph is written and no contraction runs.
+ *   status[g] = 2 no tree exists over the allowed arcs: nothing is written.
+ *   status[g] = 1 pred[g][i][0], i in 1..n-1, is overwritten with a tree that
+ *                 maximises the sum of scores[g][i][head_i] over all trees
+ *                 (Chu-Liu/Edmonds; which of several optimal trees is chosen
+ *                 is fixed by index order, the same from launch to launch).
+ * The label column, row 0 and rows >= n are never written.  With gold and
+ * counts (both, or both NULL) a repaired graph's counts[g][1] (las) and
+ * counts[g][2] (uas) are recounted from the new heads by ggnn_heads_decode's
+ * rule (rows with gold[g][i][0] >= 0); every other counter and every other
+ * graph's counts stay.
+ * Exactness: the arithmetic is 64-bit integer, and the result is exact for
+ * EVERY int32 score other than GGNN_TREE_FORBIDDEN: a sum has at most 255
+ * terms below 2^31, and single_root is a penalty of 2^42 per ROOT arc, which
+ * exceeds any difference of two trees' totals (< 2^40); adjusted scores stay
+ * within [-2^43, 2^31].  (tree_scores keeps S * v * (v + 1) < 2^30, S the
+ * largest absolute score, so the totals also fit int32.)
+ * Needs v <= o, v <= GGNN_TREE_MAXV and o <= 1024.  The kernel needs no
+ * scratch: ggnn_tree_decode_workspace_bytes returns 0 and workspace may be
+ * NULL.  Every loop of the kernel is bounded by a function of n.  Stream-
+ * ordered, legal under stream capture, bit-reproducible; booked under the
+ * heads kernel kind. */
+#define GGNN_TREE_MAXV 256
+#define GGNN_TREE_FORBIDDEN INT32_MIN
+size_t ggnn_tree_decode_workspace_bytes(int32_t b, int32_t v);
+int ggnn_tree_decode(const ggnn_dims* d,      /* b, v used */
+                     const int32_t* scores,   /* device [b][v][o] */
+                     int32_t o,
+                     const int32_t* n_nodes,  /* device [b] */
+                     int32_t single_root,     /* 0 / 1 */
+                     int32_t* pred,           /* device [b][v][2], in/out: ggnn_heads_decode's */
+                     const int32_t* gold,     /* device [b][v][2] or NULL */
+                     int32_t* counts,         /* device [b][GGNN_DECODE_COUNTS] in/out, or NULL (with gold) */
+                     int32_t* status,         /* device [b] out */
+                     void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */
