@@ -22,6 +22,7 @@
 #include "k_head.h"
 #include "k_decode.h"
 #include "k_tree.h"
+#include "k_proj.h"
 #include "k_gemm.h"
 #include "k_gemm_ring.h"
 #include "k_generic.h"
@@ -1781,6 +1782,44 @@ int ggnn_tree_decode(const ggnn_dims* d, const int32_t* scores, int32_t o, const
   hipLaunchKernelGGL(k_tree_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
                      (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
                      (int*)status);
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+
+// the projective post-pass on ggnn_heads_decode's pred (k_proj.h); booked under
+// the heads kind
+static_assert(GGNN_PROJ_LDS_MAXN == PROJ_LDS_MAXN, "projective decode constants");
+size_t ggnn_projective_decode_workspace_bytes(int32_t b, int32_t v) {
+  if (b < 1 || v <= GGNN_PROJ_LDS_MAXN) return 0;
+  return (size_t)b * 8 * (size_t)v * ((size_t)v + 1);
+}
+int ggnn_projective_decode(const ggnn_dims* d, const int32_t* scores, int32_t o, const int32_t* n_nodes,
+                           int32_t single_root, int32_t* pred, const int32_t* gold, int32_t* counts,
+                           int32_t* status, void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  if (!d) return fail(GGNN_EINVAL, "projective_decode: dims is NULL");
+  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "projective_decode: b, v must be >= 1");
+  if (o < 1 || o > HEAD_MAXO)
+    return fail(GGNN_EINVAL, "projective_decode: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
+                                 std::to_string(o) + ")");
+  if (d->v > o)
+    return fail(GGNN_EINVAL, "projective_decode: v " + std::to_string(d->v) + " > o " + std::to_string(o));
+  if (d->v > GGNN_TREE_MAXV)
+    return fail(GGNN_EINVAL, "projective_decode: v " + std::to_string(d->v) + " > GGNN_TREE_MAXV " +
+                                 std::to_string(GGNN_TREE_MAXV));
+  if (single_root != 0 && single_root != 1)
+    return fail(GGNN_EINVAL, "projective_decode: single_root must be 0 or 1");
+  if (!scores || !n_nodes || !pred || !status) return fail(GGNN_EINVAL, "projective_decode: NULL pointer");
+  if ((gold == nullptr) != (counts == nullptr))
+    return fail(GGNN_EINVAL, "projective_decode: gold and counts must be given together (one is NULL)");
+  const size_t need = ggnn_projective_decode_workspace_bytes(d->b, d->v);
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(GGNN_EINVAL, "projective_decode: workspace of " + std::to_string(workspace ? workspace_bytes : 0) +
+                                 " bytes, " + std::to_string(need) + " needed");
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_projective_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
+                     (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
+                     (int*)status, need ? (int*)workspace : nullptr, (long)(2 * (long)d->v * (d->v + 1)));
   LAUNCHCHK();
   return GGNN_OK;
 }

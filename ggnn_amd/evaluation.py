@@ -505,3 +505,175 @@ def tree_decode_arrays(scores, n_nodes, pred, single_root=True, gold=None, count
         if levels is not None:
             levels.append(lv)
     return pred, counts, status
+
+
+# -------------------------------------------------------- projective decoding
+# Host form of ``ggnn_projective_decode`` (include/ggnn.h, csrc/k_proj.h):
+# Eisner's span dynamic programme, vectorised over the spans of one length.
+PROJ_LDS_MAXN = 128            # GGNN_PROJ_LDS_MAXN
+_PROJ_NEG = -2 ** 30           # a span without a derivation; no total reaches it (the range rule)
+
+
+def is_projective(heads, n):
+    """heads[i] for the words 1..n-1 (heads[0] is ignored; node 0 is the
+    leftmost position): no two arcs (i, heads[i]), (j, heads[j]) have
+    endpoints a < c < b < d, ROOT arcs included."""
+    n = int(n)
+    if n < 3:
+        return True
+    h = np.asarray([int(x) for x in heads[1:n]], np.int64)
+    w = np.arange(1, n)
+    lo, hi = np.minimum(w, h), np.maximum(w, h)
+    return not bool(((lo[:, None] < lo[None, :]) & (lo[None, :] < hi[:, None]) & (hi[:, None] < hi[None, :])).any())
+
+
+def _proj_add(a, b):
+    return np.where((a == _PROJ_NEG) | (b == _PROJ_NEG), _PROJ_NEG, a + b)
+
+
+def _eisner(s, n, single_root):
+    """The best projective tree of one graph in the kernel's formulation (the
+    tables by diagonals T[d, s] = span s..s+d, the smallest split point or
+    ROOT child among equals).  Returns heads (list, [0] is -1) or None."""
+    lo = 1 if single_root else 0
+    m = n - lo
+    full = np.asarray(s)[:n, :n].astype(np.int64)
+    w = full[lo:, lo:].copy()                  # w[i, j]: position i takes head at position j
+    w[full[lo:, lo:] == TREE_FORBIDDEN] = _PROJ_NEG
+    w[np.arange(m), np.arange(m)] = _PROJ_NEG
+    if not single_root:
+        w[0, :] = _PROJ_NEG                    # node 0 is never a dependent
+    TR = np.full((m, m), _PROJ_NEG, np.int64)  # complete, headed at the left end
+    TL = TR.copy()                             # complete, headed at the right end
+    UR, UL = TR.copy(), TR.copy()              # incomplete, arc s -> t / t -> s
+    TR[0, :] = TL[0, :] = 0
+    for L in range(1, m):
+        st = np.arange(m - L)
+        k = np.arange(L)[:, None]
+        base = _proj_add(TR[k, st], TL[L - 1 - k, st + k + 1]).max(axis=0)
+        UR[L, st] = _proj_add(base, w[st + L, st])
+        UL[L, st] = _proj_add(base, w[st, st + L])
+        TR[L, st] = _proj_add(UR[k + 1, st], TR[L - 1 - k, st + k + 1]).max(axis=0)
+        TL[L, st] = _proj_add(TL[k, st], UL[L - k, st + k]).max(axis=0)
+    heads = [-1] * n
+    stack = []
+
+    def push(kind, a, b):
+        if a != b or kind >= 2:
+            stack.append((kind, a, b))
+
+    if single_root:
+        p = np.arange(m)
+        root = full[1:, 0].copy()
+        root[root == TREE_FORBIDDEN] = _PROJ_NEG
+        tot = _proj_add(_proj_add(TL[p, 0], TR[m - 1 - p, p]), root)
+        if tot.max() == _PROJ_NEG:
+            return None
+        r = int(np.argmax(tot))                # the first maximum
+        heads[lo + r] = 0
+        push(1, 0, r)
+        push(0, r, m - 1)
+    else:
+        if TR[m - 1, 0] == _PROJ_NEG:
+            return None
+        push(0, 0, m - 1)
+    while stack:
+        kind, a, b = stack.pop()
+        L = b - a
+        k = np.arange(L)
+        if kind == 0:
+            c, target = _proj_add(UR[k + 1, a], TR[L - 1 - k, a + k + 1]), TR[L, a]
+        elif kind == 1:
+            c, target = _proj_add(TL[k, a], UL[L - k, a + k]), TL[L, a]
+        else:
+            c = _proj_add(TR[k, a], TL[L - 1 - k, a + k + 1])
+            if kind == 2:
+                heads[lo + b] = lo + a
+                target = UR[L, a] - w[b, a]
+            else:
+                heads[lo + a] = lo + b
+                target = UL[L, a] - w[a, b]
+        f = int(np.flatnonzero((c != _PROJ_NEG) & (c == target))[0])
+        if kind == 0:
+            push(2, a, a + f + 1)
+            push(0, a + f + 1, b)
+        elif kind == 1:
+            push(1, a, a + f)
+            push(3, a + f, b)
+        else:
+            push(0, a, a + f)
+            push(1, a + f + 1, b)
+    return heads
+
+
+def projective_decode_arrays(scores, n_nodes, pred, single_root=True, gold=None, counts=None):
+    """The host form of ``ggnn_projective_decode`` (include/ggnn.h): the
+    arguments of tree_decode_arrays.  Returns (pred, counts, status): copies
+    with every graph whose heads pred[g, 1:n, 0] are not a projective tree over
+    the allowed arcs (status 1) given a projective tree of maximum total score
+    (Eisner; the smallest split point or ROOT child among equals) and its las /
+    uas recounted; status 0 = already a projective tree (or n < 2), 2 = S *
+    (n - 1) >= 2^30 for the largest absolute allowed score S, or no projective
+    tree exists; those graphs are returned as passed in."""
+    s = np.asarray(scores)
+    if s.ndim != 3 or s.dtype != np.int32:
+        raise ValueError("scores must be int32 [b, v, o]")
+    b, v, o = s.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("projective decode needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    pred = np.array(pred, np.int32)
+    if pred.shape != (b, v, 2):
+        raise ValueError("pred must be [%d, %d, 2]" % (b, v))
+    if (gold is None) != (counts is None):
+        raise ValueError("gold and counts are given together")
+    if counts is not None:
+        counts = np.array(counts, np.int32)
+        gold = np.asarray(gold)
+    nn = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
+    if nn.shape[0] != b:
+        raise ValueError("n_nodes: %d values for %d graphs" % (nn.shape[0], b))
+    status = np.zeros(b, np.int32)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2 or (is_tree(pred[g, :, 0], n, single_root, s[g]) and is_projective(pred[g, :, 0], n)):
+            continue
+        a = s[g, 1:n, :n].astype(np.int64)
+        live = a != TREE_FORBIDDEN
+        live[np.arange(n - 1), np.arange(1, n)] = False
+        heads = None
+        if int(np.abs(a[live]).max(initial=0)) * (n - 1) < 2 ** 30:
+            heads = _eisner(s[g], n, single_root)
+        if heads is None:
+            status[g] = 2
+            continue
+        status[g] = 1
+        pred[g, 1:n, 0] = heads[1:]
+        if counts is not None:
+            has = gold[g, 1:, 0] >= 0
+            hit_h = has & (pred[g, 1:, 0] == gold[g, 1:, 0])
+            counts[g, 1] = int((hit_h & (pred[g, 1:, 1] == gold[g, 1:, 1])).sum())
+            counts[g, 2] = int(hit_h.sum())
+    return pred, counts, status
+
+
+def random_projective_heads(n, rng):
+    """A random projective single-rooted tree over nodes 0..n-1 (heads[0] =
+    -1), drawn by random shift / left-arc / right-arc transitions of a stack
+    parser: ROOT stays at the bottom of the stack and takes its one child last."""
+    n = int(n)
+    heads = [-1] * n
+    stack, nxt = [0], 1
+    while nxt < n or len(stack) > 2:
+        if len(stack) > 2 and (nxt >= n or rng.random() < 0.5):
+            if rng.random() < 0.5:
+                heads[stack[-1]] = stack[-2]     # right-arc
+                stack.pop()
+            else:
+                heads[stack[-2]] = stack[-1]     # left-arc
+                del stack[-2]
+        else:
+            stack.append(nxt)
+            nxt += 1
+    if len(stack) == 2:
+        heads[stack[1]] = 0
+    return heads

@@ -173,6 +173,7 @@ class OutputHeads:
         self._lib = _lib.load()
         self._ws = None
         self._tree_ws = None   # ggnn_tree_decode's workspace (the kernel asks for none today)
+        self._proj_ws = None   # ggnn_projective_decode's workspace (graphs above PROJ_LDS_MAXN nodes)
         self._saved = None
 
     def _table(self, heads, labels, probs, dws=None, dbs=None):
@@ -284,23 +285,7 @@ class OutputHeads:
         status int32 [b]: 0 = pred's heads already were a tree, 1 = replaced
         by the maximum spanning tree of the scores, 2 = no tree exists (the
         graph is left as it was)."""
-        if scores.dim() != 3 or scores.dtype != torch.int32 or scores.device.type != "cuda":
-            raise ValueError("scores must be an int32 [b, v, o] tensor on the GPU")
-        if not scores.is_contiguous():
-            raise ValueError("scores must be contiguous")
-        b, v, o = scores.shape
-        dev = scores.device
-        if v > o or v > _lib.TREE_MAXV:
-            raise ValueError("tree_decode needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
-        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
-            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
-        if (gold is None) != (counts is None):
-            raise ValueError("gold and counts are given together")
-        for t, name, shape in ((pred, "pred", (b, v, 2)), (gold, "gold", (b, v, 2)),
-                               (counts, "counts", (b, _lib.DECODE_COUNTS))):
-            if t is not None and (t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape
-                                  or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous int32 %s tensor on %s" % (name, list(shape), dev))
+        b, v, o, dev = _tree_args("tree_decode", scores, n_nodes, pred, gold, counts)
         need = int(self._lib.ggnn_tree_decode_workspace_bytes(b, v))
         if need and (self._tree_ws is None or self._tree_ws.numel() < need or self._tree_ws.device != dev):
             self._tree_ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -311,6 +296,56 @@ class OutputHeads:
                                               _ptr(self._tree_ws) if need else None, need, _stream()),
                    "ggnn_tree_decode")
         return status
+
+    def projective_decode(self, scores, n_nodes, pred, gold=None, counts=None, single_root=True, workspace=None):
+        """The projective post-pass on ``decode``'s pred, on the same stream
+        (ggnn_projective_decode): tree_decode's arguments and checks.  Returns
+        status int32 [b]: 0 = pred's heads already were a projective tree, 1 =
+        replaced by the best projective tree of the scores (Eisner), 2 = no
+        projective tree exists or the scores are out of range (the graph is
+        left as it was).  workspace: a uint8 tensor to use instead of the
+        binding's own (grown on demand; needed for v > PROJ_LDS_MAXN only)."""
+        b, v, o, dev = _tree_args("projective_decode", scores, n_nodes, pred, gold, counts)
+        need = int(self._lib.ggnn_projective_decode_workspace_bytes(b, v))
+        if workspace is None:
+            if need and (self._proj_ws is None or self._proj_ws.numel() < need or self._proj_ws.device != dev):
+                self._proj_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = self._proj_ws if need else None
+        elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+            raise ValueError("workspace must be a contiguous uint8 tensor on %s" % dev)
+        elif workspace.numel() < need:
+            raise ValueError("workspace of %d bytes, %d needed" % (workspace.numel(), need))
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_projective_decode(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes),
+                                                    int(bool(single_root)), _ptr(pred), _ptr(gold), _ptr(counts),
+                                                    _ptr(status), _ptr(workspace),
+                                                    0 if workspace is None else workspace.numel(), _stream()),
+                   "ggnn_projective_decode")
+        return status
+
+
+def _tree_args(name, scores, n_nodes, pred, gold, counts):
+    """The argument checks tree_decode and projective_decode share; returns
+    (b, v, o, device)."""
+    if scores.dim() != 3 or scores.dtype != torch.int32 or scores.device.type != "cuda":
+        raise ValueError("scores must be an int32 [b, v, o] tensor on the GPU")
+    if not scores.is_contiguous():
+        raise ValueError("scores must be contiguous")
+    b, v, o = scores.shape
+    dev = scores.device
+    if v > o or v > _lib.TREE_MAXV:
+        raise ValueError("%s needs v <= o and v <= %d (got v %d, o %d)" % (name, _lib.TREE_MAXV, v, o))
+    if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
+        raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
+    if (gold is None) != (counts is None):
+        raise ValueError("gold and counts are given together")
+    for t, what, shape in ((pred, "pred", (b, v, 2)), (gold, "gold", (b, v, 2)),
+                           (counts, "counts", (b, _lib.DECODE_COUNTS))):
+        if t is not None and (t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape
+                              or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous int32 %s tensor on %s" % (what, list(shape), dev))
+    return b, v, o, dev
 
 
 def tree_score_shift(v):

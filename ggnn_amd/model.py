@@ -30,7 +30,10 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
   ``score_epoch`` (the scores from per-graph counts), decoded on the device by
   ``ggnn_heads_decode`` (``csrc/k_decode.h``); with ``tree=True`` the heads
   of a graph that is not a dependency tree are replaced by the maximum
-  spanning tree of the head scores (``ggnn_tree_decode``, ``csrc/k_tree.h``)
+  spanning tree of the head scores (``ggnn_tree_decode``, ``csrc/k_tree.h``),
+  with ``tree="projective"`` the heads of a graph that is not a projective
+  tree by the best projective tree (``ggnn_projective_decode``,
+  ``csrc/k_proj.h``)
 
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
@@ -72,6 +75,16 @@ GRU_KEYS = ("gates_kernel", "gates_bias", "candidate_kernel", "candidate_bias")
 PATH_KEYS = ("edge_weights", "edge_biases") + GRU_KEYS
 KEEP_KEYS = ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weight_dropout_keep_prob",
              "emb_dropout_keep_prob")
+
+
+def _tree_mode(tree):
+    """The ``tree`` keyword of the decoding entries: False, True or
+    "projective" (returned as given); anything else is a ValueError."""
+    if isinstance(tree, (bool, np.bool_)):
+        return bool(tree)
+    if isinstance(tree, str) and tree == "projective":
+        return tree
+    raise ValueError('tree must be False, True or "projective", got %r' % (tree,))
 
 
 def mlp_init(shape, rng):
@@ -869,8 +882,10 @@ class DenseGGNNChemModel(BtbBatching):
         (ggnn_heads_decode; only [b, 5] int32 leave the device).  tree (with
         on_device): the heads of every graph that is not a tree are replaced by
         the maximum spanning tree before the counts are read (ggnn_tree_decode,
-        as predict_batch(tree=True) returns them)."""
-        if tree and not on_device:
+        as predict_batch(tree=True) returns them); tree="projective": by the
+        best projective tree when they are not a projective tree
+        (ggnn_projective_decode).  Any other value of tree raises ValueError."""
+        if _tree_mode(tree) and not on_device:
             raise ValueError("evaluate_batch: tree=True needs on_device=True")
         if on_device:
             r = self._decode_forward(feed_dict, True, tree, single_root)
@@ -967,7 +982,10 @@ class DenseGGNNChemModel(BtbBatching):
         without n_nodes.  tree: the tree post-pass follows the decode eagerly
         on the same stream (never inside a captured step) and 'tree_status'
         [b] joins the dict; a graph with regular == 0 is not passed to it
-        (node count 0) and gets status 2."""
+        (node count 0) and gets status 2.  tree="projective": the projective
+        pass (ggnn_projective_decode, the host form on a CPU device) takes the
+        MST pass's place, on the same scores and with the same status rules."""
+        projective = _tree_mode(tree) == "projective"
         loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
         ph = dict(self.placeholders)
         b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
@@ -987,7 +1005,8 @@ class DenseGGNNChemModel(BtbBatching):
             r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(probs.numpy(), probs_e.numpy(), n, y, y_e)
             if tree:
                 regular = r["counts"][:, 4] == 1
-                pred, counts, status = _eval.tree_decode_arrays(
+                host_pass = _eval.projective_decode_arrays if projective else _eval.tree_decode_arrays
+                pred, counts, status = host_pass(
                     _eval.tree_scores(probs.numpy(), n, v), np.where(regular, n, 0), r["pred"], single_root,
                     r["gold"], r["counts"] if with_gold else None)
                 r["pred"], r["tree_status"] = pred, np.where(regular, status, 2).astype(np.int32)
@@ -999,7 +1018,8 @@ class DenseGGNNChemModel(BtbBatching):
             [probs, probs_e], n_dev, self._last_labels if with_gold else None)
         if tree:
             regular = r["counts"][:, 4] == 1
-            status = self._decode_heads().tree_decode(
+            heads = self._decode_heads()
+            status = (heads.projective_decode if projective else heads.tree_decode)(
                 tree_scores(probs, n_dev, v), (n_dev * regular).to(torch.int32), r["pred"], r["gold"],
                 r["counts"] if with_gold else None, single_root)
             r["tree_status"] = torch.where(regular, status, torch.full_like(status, 2))
@@ -1026,7 +1046,14 @@ class DenseGGNNChemModel(BtbBatching):
         maximum spanning tree of the head scores instead (ggnn_tree_decode on
         tree_scores of the head probabilities) and 'tree_status' [b] int32
         says 0 = was a tree, 1 = repaired, 2 = no tree exists / not attempted
-        (left as the arg-max); None without tree."""
+        (left as the arg-max); None without tree.  tree="projective": 'heads'
+        of a graph whose arg-max heads are not a PROJECTIVE dependency tree
+        (no two arcs cross, ROOT at the leftmost position) hold the best
+        projective tree of the same scores instead (ggnn_projective_decode,
+        Eisner's algorithm); the MST pass does not run, and 'tree_status' says
+        0 = was a projective tree, 1 = repaired, 2 = no projective tree exists
+        / not attempted.  tree must be False, True or "projective"."""
+        tree = _tree_mode(tree)
         r = self._decode_forward(feed_dict, False, tree, single_root)
         ph, b, v = r["ph"], r["b"], r["v"]
         pred = r["pred"]
@@ -1054,7 +1081,10 @@ class DenseGGNNChemModel(BtbBatching):
         is_probability=True) + merge_head_and_edge_graph give for the sentence.
         A sentence process_raw_graphs drops (empty graph) yields [].  tree: as
         predict_batch(tree=True): every sentence for which a dependency tree
-        exists comes back as one."""
+        exists comes back as one.  tree="projective": every sentence for which
+        a projective dependency tree exists comes back as one (no crossing
+        arcs; predict_batch(tree="projective"))."""
+        tree = _tree_mode(tree)
         raw = []
         for k, d in enumerate(raw_data):
             c = dict(d)
@@ -1083,7 +1113,11 @@ class DenseGGNNChemModel(BtbBatching):
         the scores are those of the tree-constrained heads (ggnn_tree_decode
         after the decode, its status [b] fetched beside the counts);
         ``decode_stats`` counts the repaired graphs and those without a tree
-        (a graph on the host fallback is scored from its arg-max lists)."""
+        (a graph on the host fallback is scored from its arg-max lists).
+        tree="projective": the same with the projective pass
+        (ggnn_projective_decode) in the MST pass's place; the same keys count
+        the graphs it repaired and those without a projective tree."""
+        tree = _tree_mode(tree)
         stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0, "repaired_graphs": 0,
                                      "infeasible_graphs": 0}
 

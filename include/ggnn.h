@@ -457,6 +457,53 @@ int ggnn_tree_decode(const ggnn_dims* d,      /* b, v used */
                      int32_t* status,         /* device [b] out */
                      void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* Projective decoding: the same post-pass with the best PROJECTIVE tree
+ * (Eisner's O(n^3) span dynamic programme) in place of the maximum spanning
+ * tree.  Arguments, allowed arcs, the tree rule and the clamping of n are
+ * ggnn_tree_decode's; node 0 (ROOT) is the leftmost position.  A tree is
+ * projective when no two of its arcs (i, head_i), (j, head_j) have endpoints
+ * a < c < b < d, ROOT arcs included.
+ *   status[g] = 0 pred[g][1..n-1][0] as passed in is a projective tree (with
+ *                 single_root: with one ROOT child), or n < 2: nothing of the
+ *                 graph is written and no table is filled.
+ *   status[g] = 2 S * (n - 1) >= 2^30, S the largest absolute allowed score of
+ *                 the graph (the range rule: below it every span total fits
+ *                 int32, and the tables are int32), or no projective tree
+ *                 exists over the allowed arcs: nothing is written.
+ *   status[g] = 1 pred[g][i][0], i in 1..n-1, is overwritten with a projective
+ *                 tree that maximises the sum of scores[g][i][head_i] over all
+ *                 projective trees.  Among equal candidates the smallest split
+ *                 point or ROOT child wins: the same bytes from launch to
+ *                 launch.
+ * single_root = 1 runs the tables over the words 1..n-1 and adds ROOT's one arc
+ * at the end (no penalty constants); single_root = 0 runs them over 0..n-1
+ * with node 0 never a dependent.  A span without a derivation holds -2^30
+ * exactly, which no total can reach and which is never added to.
+ * The label column, row 0 and rows >= n are never written.  gold / counts:
+ * as ggnn_tree_decode (las and uas of a repaired graph recounted, every other
+ * counter stays).
+ * Storage: a graph with n <= GGNN_PROJ_LDS_MAXN keeps its four triangular
+ * int32 tables (8 n (n + 1) bytes) in LDS, a larger one in `workspace`
+ * (per graph; the tier follows the graph's n, not v).
+ * ggnn_projective_decode_workspace_bytes(b, v) is 0 for v <=
+ * GGNN_PROJ_LDS_MAXN and b * 8 * v * (v + 1) above; a smaller workspace is
+ * rejected.  Needs v <= o, v <= GGNN_TREE_MAXV and o <= 1024.  One workgroup
+ * per graph, no atomics, every loop bounded by a function of n.  Stream-
+ * ordered, legal under stream capture, bit-reproducible; booked under the
+ * heads kernel kind. */
+#define GGNN_PROJ_LDS_MAXN 128
+size_t ggnn_projective_decode_workspace_bytes(int32_t b, int32_t v);
+int ggnn_projective_decode(const ggnn_dims* d,      /* b, v used */
+                           const int32_t* scores,   /* device [b][v][o] */
+                           int32_t o,
+                           const int32_t* n_nodes,  /* device [b] */
+                           int32_t single_root,     /* 0 / 1 */
+                           int32_t* pred,           /* device [b][v][2], in/out: ggnn_heads_decode's */
+                           const int32_t* gold,     /* device [b][v][2] or NULL */
+                           int32_t* counts,         /* device [b][GGNN_DECODE_COUNTS] in/out, or NULL (with gold) */
+                           int32_t* status,         /* device [b] out */
+                           void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */

@@ -14,6 +14,20 @@ softmax of N(0, 0.1^2) logits over the real columns: the arg-max is close to
 random and nearly every graph is repaired, the worst case); "peaked" -- 0.9 on
 a gold tree's arcs: every graph takes the fast path.  The device and host
 statuses and tree totals are compared on the way.
+
+    python tools/ab_tree_decode.py --projective [--epoch]
+
+alternates, in the same process, the MST path above with decode +
+ggnn_projective_decode on the same inputs and adds to every line
+  decode_proj_ms   ggnn_heads_decode + ggnn_projective_decode
+  proj_ms          decode_proj_ms - decode_ms (beside tree_ms)
+  proj_status      graphs with status 0 / 1 / 2 (beside status, the MST's)
+  host_proj_ms     the fetch + evaluation.projective_decode_arrays
+and a third regime, "peaked-projective": 0.9 on a random PROJECTIVE gold
+tree's arcs, so every graph takes the projective fast path ("peaked"'s gold
+trees generally cross: there the arg-max is a non-projective tree, the MST
+pass takes its fast path and the projective pass repairs every graph with few
+changes).  --epoch then also scores the dev set with tree="projective".
 """
 import argparse
 import json
@@ -34,9 +48,13 @@ def batch(b, v, o, oe, regime, seed):
     for g in range(b):
         k = int(n[g])
         logits = rng.normal(0, 0.1, (v, k))
-        if regime == "peaked":
+        if regime != "flat":
             gold = np.zeros(v, int)
-            gold[2:k] = [rng.integers(1, i) for i in range(2, k)]     # word 1 is the one ROOT child
+            if regime == "peaked":
+                gold[2:k] = [rng.integers(1, i) for i in range(2, k)]     # word 1 is the one ROOT child
+            else:                                                     # peaked-projective
+                from ggnn_amd.evaluation import random_projective_heads
+                gold[1:k] = random_projective_heads(k, rng)[1:]
             logits[np.arange(1, k), gold[1:k]] += np.log(9.0 * (k - 1))
         e = np.exp(logits - logits.max(axis=1, keepdims=True))
         ph[g, :, :k] = e / e.sum(axis=1, keepdims=True)
@@ -60,13 +78,32 @@ def timed(torch, fn, warmup=5, rounds=5, calls=40):
     return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
-def kernel_sizes(torch, sizes):
+def alternated(torch, fns, warmup=5, rounds=5, calls=40):
+    """timed() of several paths with their rounds interleaved: (median, min, max) per path."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            z.record()
+            z.synchronize()
+            ms[k].append(a.elapsed_time(z) / calls)
+    return [(float(np.median(x)), float(min(x)), float(max(x))) for x in ms]
+
+
+def kernel_sizes(torch, sizes, projective=False):
     from ggnn_amd import evaluation as E
     from ggnn_amd.heads import OutputHeads, tree_scores
     dev = torch.device("cuda", 0)
     oh = OutputHeads(64)
     for (b, v, o) in sizes:
-        for regime in ("flat", "peaked"):
+        for regime in ("flat", "peaked") + (("peaked-projective",) if projective else ()):
             ph, pe, n = batch(b, v, o, 46, regime, seed=b + v)
             ph_d, pe_d, n_d = (torch.from_numpy(x).to(dev) for x in (ph, pe, n))
             scores = tree_scores(ph_d, n_d, v)
@@ -100,10 +137,37 @@ def kernel_sizes(torch, sizes):
                 assert E.tree_total(s_h[g], pred[g, :, 0], n_h[g]) == E.tree_total(s_h[g], h_pred[g, :, 0], n_h[g])
             out["status"] = [int((status == k).sum()) for k in (0, 1, 2)]
             out["device_faster_than_host"] = out["tree_ms"] < out["host_ms"]
+            if projective:
+                def with_proj():
+                    pred, _, _ = oh.decode([ph_d, pe_d], n_d)
+                    return pred, oh.projective_decode(scores, n_d, pred)
+
+                calls = 40 if b * v <= 2048 or regime == "peaked-projective" else 10
+                (t_plain, t_tree, t_proj) = alternated(torch, [plain, with_tree, with_proj], calls=calls)
+                out["decode_ms"], out["decode_ms_min"], out["decode_ms_max"] = t_plain
+                out["decode_tree_ms"], out["decode_tree_ms_min"], out["decode_tree_ms_max"] = t_tree
+                out["decode_proj_ms"], out["decode_proj_ms_min"], out["decode_proj_ms_max"] = t_proj
+                out["tree_ms"] = t_tree[0] - out["decode_ms"]
+                out["proj_ms"] = t_proj[0] - out["decode_ms"]
+                pred, status = with_proj()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                s_h, n_h, p_h = scores.cpu().numpy(), n_d.cpu().numpy(), pred0.cpu().numpy()
+                h_pred, _, h_status = E.projective_decode_arrays(s_h, n_h, p_h, True)
+                out["host_proj_ms"] = (time.perf_counter() - t) * 1e3
+                status, pred = status.cpu().numpy(), pred.cpu().numpy()
+                assert np.array_equal(status, h_status)
+                changed = 0
+                for g in np.flatnonzero(status == 1):
+                    assert E.is_tree(pred[g, :, 0], n_h[g], True, s_h[g]) and E.is_projective(pred[g, :, 0], n_h[g])
+                    assert E.tree_total(s_h[g], pred[g, :, 0], n_h[g]) == E.tree_total(s_h[g], h_pred[g, :, 0], n_h[g])
+                    changed += int((pred[g, 1:n_h[g], 0] != p_h[g, 1:n_h[g], 0]).sum())
+                out["proj_status"] = [int((status == k).sum()) for k in (0, 1, 2)]
+                out["proj_heads_changed"] = changed
             print(json.dumps(out), flush=True)
 
 
-def epoch(torch):
+def epoch(torch, projective=False):
     from ggnn_amd import evaluation as E
     from ggnn_amd.batching import DATA_DIR, TRAIN_WITH_DEV, read_btb_json, wsj_model_sizes
     from ggnn_amd.model import DenseGGNNChemModel
@@ -114,8 +178,13 @@ def epoch(torch):
     m.score_epoch(data)
     m.score_epoch(data, tree=True)                                    # both paths warm
     out = {"what": "score_epoch, 1700 dev sentences, batch 20, untrained model", "plain_s": [], "tree_s": []}
+    paths = (("plain_s", {}), ("tree_s", {"tree": True}))
+    if projective:
+        m.score_epoch(data, tree="projective")
+        out["projective_s"] = []
+        paths += (("projective_s", {"tree": "projective"}),)
     for _ in range(3):                                                # alternating
-        for key, kw in (("plain_s", {}), ("tree_s", {"tree": True})):
+        for key, kw in paths:
             torch.cuda.synchronize()
             t = time.perf_counter()
             r = m.score_epoch(data, **kw)
@@ -136,19 +205,33 @@ def epoch(torch):
                       and E.is_tree([-1] + [x[0] for x in p], len(p) + 1, True))
     print(json.dumps({"what": "parse(dev, tree=True)", "sentences": len(raw), "single_rooted_trees": trees,
                       "arg_max_trees": plain_trees, "parse_tree_s": round(secs, 3)}), flush=True)
+    if projective:
+        t = time.perf_counter()
+        proj = m.parse(raw, tree="projective")
+        secs = time.perf_counter() - t
+        count = lambda ps: sum(1 for d, p in zip(raw, ps)
+                               if len(p) == len(d["node_features"]) - 1
+                               and E.is_tree([-1] + [x[0] for x in p], len(p) + 1, True)
+                               and E.is_projective([-1] + [x[0] for x in p], len(p) + 1))
+        print(json.dumps({"what": 'parse(dev, tree="projective")', "sentences": len(raw),
+                          "projective_trees": count(proj), "mst_projective_trees": count(parsed),
+                          "arg_max_projective_trees": count(plain), "parse_projective_s": round(secs, 3)}),
+              flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epoch", action="store_true", help="also time score_epoch and check parse on the dev set")
+    ap.add_argument("--projective", action="store_true",
+                    help="alternate the MST pass with ggnn_projective_decode (and tree=\"projective\" with --epoch)")
     ap.add_argument("--sizes", default="20x40x150,256x128x150")
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "ab_tree_decode.py needs a HIP device"
     print(json.dumps({"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}), flush=True)
-    kernel_sizes(torch, [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")])
+    kernel_sizes(torch, [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")], args.projective)
     if args.epoch:
-        epoch(torch)
+        epoch(torch, args.projective)
 
 
 if __name__ == "__main__":
