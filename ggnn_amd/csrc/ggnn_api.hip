@@ -23,6 +23,7 @@
 #include "k_decode.h"
 #include "k_tree.h"
 #include "k_proj.h"
+#include "k_marg.h"
 #include "k_gemm.h"
 #include "k_gemm_ring.h"
 #include "k_generic.h"
@@ -1820,6 +1821,64 @@ int ggnn_projective_decode(const ggnn_dims* d, const int32_t* scores, int32_t o,
   hipLaunchKernelGGL(k_projective_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
                      (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
                      (int*)status, need ? (int*)workspace : nullptr, (long)(2 * (long)d->v * (d->v + 1)));
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+
+// projective arc marginals and the gather of the predicted heads' marginals
+// (k_marg.h); booked under the heads kind
+static_assert(GGNN_MARG_LDS_MAXN == MARG_LDS_MAXN, "projective marginals constants");
+static_assert(sizeof(float) * (MARG_TABLES * PROJ_TRI(MARG_LDS_MAXN) + TREE_MAXV + 2) <= 160 * 1024 &&
+                  sizeof(float) * (MARG_TABLES * PROJ_TRI(MARG_LDS_MAXN + 1) + TREE_MAXV + 2) > 160 * 1024,
+              "GGNN_MARG_LDS_MAXN is the largest n whose tables fit the LDS of a CU");
+size_t ggnn_projective_marginals_workspace_bytes(int32_t b, int32_t v) {
+  if (b < 1 || v <= GGNN_MARG_LDS_MAXN) return 0;
+  return (size_t)b * 2 * MARG_TABLES * (size_t)v * ((size_t)v + 1);
+}
+int ggnn_projective_marginals(const ggnn_dims* d, const float* probs_head, int32_t o, const int32_t* n_nodes,
+                              int32_t single_root, float* marg, float* logz, int32_t* scores, int32_t* status,
+                              void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  if (!d) return fail(GGNN_EINVAL, "projective_marginals: dims is NULL");
+  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "projective_marginals: b, v must be >= 1");
+  if (o < 1 || o > HEAD_MAXO)
+    return fail(GGNN_EINVAL, "projective_marginals: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
+                                 std::to_string(o) + ")");
+  if (d->v > o)
+    return fail(GGNN_EINVAL, "projective_marginals: v " + std::to_string(d->v) + " > o " + std::to_string(o));
+  if (d->v > GGNN_TREE_MAXV)
+    return fail(GGNN_EINVAL, "projective_marginals: v " + std::to_string(d->v) + " > GGNN_TREE_MAXV " +
+                                 std::to_string(GGNN_TREE_MAXV));
+  if (single_root != 0 && single_root != 1)
+    return fail(GGNN_EINVAL, "projective_marginals: single_root must be 0 or 1");
+  if (!probs_head || !n_nodes || !marg || !logz || !status)
+    return fail(GGNN_EINVAL, "projective_marginals: NULL pointer");
+  if (marg == probs_head) return fail(GGNN_EINVAL, "projective_marginals: marg must not alias probs_head");
+  const size_t need = ggnn_projective_marginals_workspace_bytes(d->b, d->v);
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(GGNN_EINVAL, "projective_marginals: workspace of " +
+                                 std::to_string(workspace ? workspace_bytes : 0) + " bytes, " + std::to_string(need) +
+                                 " needed");
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_projective_marginals, dim3((unsigned)d->b), dim3(256), 0, s, probs_head, (int)o,
+                     (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (int*)scores, (int*)status,
+                     need ? (float*)workspace : nullptr, (long)MARG_TABLES * PROJ_TRI((long)d->v));
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+int ggnn_arc_confidence(const ggnn_dims* d, const float* marg, int32_t o, const int32_t* n_nodes,
+                        const int32_t* pred, float* conf, ggnn_stream_t stream) {
+  if (!d) return fail(GGNN_EINVAL, "arc_confidence: dims is NULL");
+  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "arc_confidence: b, v must be >= 1");
+  if (o < 1 || o > HEAD_MAXO)
+    return fail(GGNN_EINVAL, "arc_confidence: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
+                                 std::to_string(o) + ")");
+  if (d->v > o) return fail(GGNN_EINVAL, "arc_confidence: v " + std::to_string(d->v) + " > o " + std::to_string(o));
+  if (!marg || !n_nodes || !pred || !conf) return fail(GGNN_EINVAL, "arc_confidence: NULL pointer");
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_arc_confidence, dim3(grid1d((long)d->b * d->v)), dim3(256), 0, s, marg, (int)o,
+                     (const int*)n_nodes, (int)d->b, (int)d->v, (const int*)pred, conf);
   LAUNCHCHK();
   return GGNN_OK;
 }

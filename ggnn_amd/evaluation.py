@@ -677,3 +677,177 @@ def random_projective_heads(n, rng):
     if len(stack) == 2:
         heads[stack[1]] = 0
     return heads
+
+
+# ------------------------------------------------- projective arc marginals
+# Host form of ``ggnn_projective_marginals`` (include/ggnn.h, csrc/k_marg.h):
+# the sum-product twin of _eisner (inside pass, explicit outside pass), in log
+# space, vectorised over the spans of one length.
+MARG_LDS_MAXN = 107            # GGNN_MARG_LDS_MAXN
+MARG_SCORE_SCALE = 2 ** 20     # scores = rint(marg * 2^20)
+
+
+def _lse(x, axis=0):
+    """log-sum-exp along an axis: the maximum first, then the sum of exp(x -
+    max); -inf where every term is -inf (no -inf is ever subtracted)."""
+    mx = x.max(axis=axis)
+    safe = np.where(mx == -np.inf, 0, mx).astype(x.dtype)
+    with np.errstate(divide="ignore"):
+        out = safe + np.log(np.exp(x - np.expand_dims(safe, axis)).sum(axis=axis, dtype=x.dtype))
+    return np.where(mx == -np.inf, -np.inf, out).astype(x.dtype)
+
+
+def _arc_log_potentials(p, n, dtype):
+    """ln p where the arc "word i takes head j" is allowed (tree_scores' rule:
+    finite, > 0, 1 <= i < n, j < n, j != i), -inf elsewhere; [n, n]."""
+    q = np.asarray(p)[:n, :n].astype(dtype)
+    ok = np.isfinite(q) & (q > 0)
+    ok[0, :] = False
+    ok[np.arange(n), np.arange(n)] = False
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(ok, np.log(np.where(ok, q, 1)), -np.inf).astype(dtype), ok
+
+
+def _inside_outside(psi, n, single_root):
+    """One graph: psi [n, n] log potentials (-inf = not allowed).  Returns
+    (logz, marg [n, n] in psi's dtype, the largest absolute finite table
+    value, ln Z included); logz = -inf when no projective tree exists."""
+    dt = psi.dtype
+    lo = 1 if single_root else 0
+    m = n - lo
+    w = psi[lo:, lo:]                                   # w[i, j]: position i takes the head at position j
+    root = psi[1:, 0] if single_root else None
+    neg = lambda: np.full((m, m), -np.inf, dt)
+    CR, CL, IR, IL = neg(), neg(), neg(), neg()         # T[d, s]: the span s..s+d, as _eisner's tables
+    CR[0, :] = CL[0, :] = 0
+    for L in range(1, m):
+        st = np.arange(m - L)
+        k = np.arange(L)[:, None]
+        base = _lse(CR[k, st] + CL[L - 1 - k, st + k + 1])
+        IR[L, st] = base + w[st + L, st]
+        IL[L, st] = base + w[st, st + L]
+        CR[L, st] = _lse(IR[k + 1, st] + CR[L - 1 - k, st + k + 1])
+        CL[L, st] = _lse(CL[k, st] + IL[L - k, st + k])
+    p = np.arange(m)
+    if single_root:
+        logz = _lse(CL[p, 0] + CR[m - 1 - p, p] + root)
+    else:
+        logz = CR[m - 1, 0]
+    tables = [CR, CL, IR, IL]
+    marg = np.zeros((n, n), dt)
+    if not np.isfinite(logz):
+        return dt.type(-np.inf), marg, 0.0
+    # the outside pass, from the longest length down: complete spans first
+    # (they gather from longer spans only), then the incomplete spans
+    oCR, oCL, oB = neg(), neg(), neg()                  # oB: outside of `base`, the lse of both arcs' outsides
+    tables += [oCR, oCL, oB]
+    for L in range(m - 1, 0, -1):
+        S = m - L
+        st = np.arange(S)
+        t = st + L
+        j = np.arange(S)[:, None]                       # j + 1 spans to the left / j + 1 to the right
+        left = j < st                                   # st - 1 - j >= 0
+        a = np.where(left, st - 1 - j, 0)
+        right = t + 1 + j <= m - 1
+        c = np.where(right, t + 1, 0)
+        d = np.where(right, L + 1 + j, 0)
+        e = np.where(left, L + 1 + j, 0)
+        with np.errstate(invalid="ignore"):
+            # CR[s][t]: the right part of CR[a][t] = IR[a][s] + CR[s][t], the left part of base[s][t']
+            x = [np.where(left, oCR[e, a] + IR[j + 1, a], -np.inf), np.where(right, oB[d, st] + CL[j, c], -np.inf)]
+            # CL[s][t]: the left part of CL[s][t'] = CL[s][t] + IL[t][t'], the right part of base[a][t]
+            y = [np.where(right, oCL[d, st] + IL[np.where(right, j + 1, 0), np.where(right, t, 0)], -np.inf),
+                 np.where(left, oB[e, a] + CR[j, a], -np.inf)]
+        ir = np.full(S, -np.inf, dt)
+        il = np.full(S, -np.inf, dt)
+        if single_root:
+            ir[S - 1] = CL[S - 1, 0] + root[S - 1]      # t = m - 1: ROOT's child is position s
+            il[0] = CR[m - 1 - L, L] + root[L]          # s = 0: ROOT's child is position t
+        elif L == m - 1:
+            ir[0] = 0
+        oCR[L, st] = _lse(np.concatenate(x + [ir[None]]).astype(dt))
+        oCL[L, st] = _lse(np.concatenate(y + [il[None]]).astype(dt))
+        # IR[s][t]: the left part of CR[s][t'], t' >= t;  IL[s][t]: the right part of CL[a][t], a <= s
+        j = np.arange(S)[:, None]
+        right = t + j <= m - 1
+        left = j <= st
+        a = np.where(left, st - j, 0)
+        oIR = _lse(np.where(right, oCR[np.where(right, L + j, 0), st] + CR[j, np.where(right, t, 0)], -np.inf).astype(dt))
+        oIL = _lse(np.where(left, oCL[np.where(left, L + j, 0), a] + CL[j, a], -np.inf).astype(dt))
+        wr, wl = w[t, st], w[st, t]
+        oB[L, st] = _lse(np.stack([oIR + wr, oIL + wl]))
+        with np.errstate(invalid="ignore"):
+            marg[lo + t, lo + st] = np.exp(np.where(np.isfinite(IR[L, st] + oIR), IR[L, st] + oIR - logz, -np.inf))
+            marg[lo + st, lo + t] = np.exp(np.where(np.isfinite(IL[L, st] + oIL), IL[L, st] + oIL - logz, -np.inf))
+    if single_root:
+        x = CL[p, 0] + CR[m - 1 - p, p] + root
+        marg[1 + p, 0] = np.exp(np.where(np.isfinite(x), x - logz, -np.inf))
+    # (ln Z counts as the last cell of the inside pass: without single_root it is CR[0][m-1] itself)
+    span_max = max([float(np.abs(T[np.isfinite(T)]).max(initial=0.0)) for T in tables] + [abs(float(logz))])
+    return logz, np.minimum(marg, 1).astype(dt), span_max
+
+
+def projective_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.float64):
+    """The host form of ``ggnn_projective_marginals`` (include/ggnn.h):
+    probs_head float32 [b, v, o], n_nodes [b].  The potential of "word i takes
+    head j" is probs_head[g, i, j] where tree_scores allows the arc; a
+    projective tree (ROOT leftmost, no crossing arcs, single_root: one ROOT
+    child) weighs the product of its words' potentials.  Returns (marg
+    [b, v, o], logz [b], scores int32 [b, v, o], status int32 [b], span_max
+    [b]): marg[g, i, j] the share of the weight of the trees with that arc (0
+    for an arc that is not allowed), logz the natural log of the total weight,
+    scores = rint(marg * 2^20) on the allowed arcs and TREE_FORBIDDEN
+    elsewhere; status 1 = written, 0 = n < 2, 2 = no projective tree exists:
+    for status != 1 marg[g] is a copy of probs_head[g] and scores[g] is
+    TREE_FORBIDDEN everywhere (logz 0 / -inf).  span_max[g]: the largest
+    absolute finite value of the inside and outside tables and of logz
+    (float; what an fp32 kernel's stored values are rounded at).  The tables
+    are kept in ``dtype``."""
+    p = np.asarray(probs_head, np.float32)
+    if p.ndim != 3:
+        raise ValueError("probs_head must be [b, v, o]")
+    b, v, o = p.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("projective marginals need v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    dt = np.dtype(dtype)
+    nn = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
+    if nn.shape[0] != b:
+        raise ValueError("n_nodes: %d values for %d graphs" % (nn.shape[0], b))
+    marg = p.astype(dt)
+    logz = np.zeros(b, dt)
+    scores = np.full((b, v, o), TREE_FORBIDDEN, np.int32)
+    status = np.zeros(b, np.int32)
+    span_max = np.zeros(b, np.float64)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2:
+            continue
+        psi, ok = _arc_log_potentials(p[g], n, dt)
+        lz, mg, span_max[g] = _inside_outside(psi, n, bool(single_root))
+        logz[g] = lz
+        if not np.isfinite(lz):
+            status[g] = 2
+            continue
+        status[g] = 1
+        marg[g] = 0
+        marg[g, :n, :n] = np.where(ok, mg, 0)
+        scores[g, :n, :n] = np.where(ok, np.rint(marg[g, :n, :n].astype(np.float32) * np.float32(MARG_SCORE_SCALE)),
+                                     TREE_FORBIDDEN).astype(np.int32)
+    return marg, logz, scores, status, span_max
+
+
+def arc_confidence_arrays(marg, n_nodes, pred):
+    """The host form of ``ggnn_arc_confidence``: conf[g, i] = marg[g, i,
+    pred[g, i, 0]] as float32, 0 where the predicted head is -1 or the row is
+    0 or >= n."""
+    mg = np.asarray(marg)
+    pred = np.asarray(pred)
+    b, v, o = mg.shape
+    if pred.shape != (b, v, 2):
+        raise ValueError("pred must be [%d, %d, 2]" % (b, v))
+    n = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
+    h = pred[:, :, 0].astype(np.int64)
+    i = np.arange(v)[None, :]
+    ok = (h >= 0) & (h < o) & (i >= 1) & (i < n[:, None])
+    got = np.take_along_axis(mg, np.where(ok, h, 0)[:, :, None], axis=2)[:, :, 0]
+    return np.where(ok, got, 0).astype(np.float32)

@@ -174,6 +174,7 @@ class OutputHeads:
         self._ws = None
         self._tree_ws = None   # ggnn_tree_decode's workspace (the kernel asks for none today)
         self._proj_ws = None   # ggnn_projective_decode's workspace (graphs above PROJ_LDS_MAXN nodes)
+        self._marg_ws = None   # ggnn_projective_marginals' workspace (graphs above MARG_LDS_MAXN nodes)
         self._saved = None
 
     def _table(self, heads, labels, probs, dws=None, dbs=None):
@@ -323,6 +324,69 @@ class OutputHeads:
                                                     0 if workspace is None else workspace.numel(), _stream()),
                    "ggnn_projective_decode")
         return status
+
+    def projective_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True, workspace=None):
+        """The posterior marginal of every arc under the distribution over
+        projective trees that the head probabilities define, on the current
+        stream (ggnn_projective_marginals).  probs_head: float32 [b, v, o];
+        n_nodes: int32 [b].  Returns (marg float32 [b, v, o], logz float32
+        [b], scores int32 [b, v, o] = rint(marg * 2^20) / GGNN_TREE_FORBIDDEN
+        (None without with_scores), status int32 [b]: 1 = written, 0 = n < 2,
+        2 = no projective tree; for status != 1 marg is a copy of probs_head
+        and scores are all forbidden).  workspace: a uint8 tensor to use
+        instead of the binding's own (grown on demand; needed for v >
+        MARG_LDS_MAXN only)."""
+        p = probs_head
+        if p.dim() != 3 or p.dtype != torch.float32 or p.device.type != "cuda":
+            raise ValueError("probs_head must be a float32 [b, v, o] tensor on the GPU")
+        if not p.is_contiguous():
+            raise ValueError("probs_head must be contiguous")
+        b, v, o = p.shape
+        dev = p.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("projective_marginals needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
+        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
+            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
+        need = int(self._lib.ggnn_projective_marginals_workspace_bytes(b, v))
+        if workspace is None:
+            if need and (self._marg_ws is None or self._marg_ws.numel() < need or self._marg_ws.device != dev):
+                self._marg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = self._marg_ws if need else None
+        elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+            raise ValueError("workspace must be a contiguous uint8 tensor on %s" % dev)
+        elif workspace.numel() < need:
+            raise ValueError("workspace of %d bytes, %d needed" % (workspace.numel(), need))
+        marg = torch.empty_like(p)
+        logz = torch.empty(b, dtype=torch.float32, device=dev)
+        scores = torch.empty(b, v, o, dtype=torch.int32, device=dev) if with_scores else None
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_projective_marginals(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes),
+                                                       int(bool(single_root)), _ptr(marg), _ptr(logz), _ptr(scores),
+                                                       _ptr(status), _ptr(workspace),
+                                                       0 if workspace is None else workspace.numel(), _stream()),
+                   "ggnn_projective_marginals")
+        return marg, logz, scores, status
+
+    def arc_confidence(self, marg, n_nodes, pred):
+        """conf float32 [b, v]: marg[g, i, pred[g, i, 0]], 0 where there is no
+        predicted head or the row is 0 or >= n (ggnn_arc_confidence).  marg:
+        float32 [b, v, o]; n_nodes: int32 [b]; pred: int32 [b, v, 2]."""
+        if marg.dim() != 3 or marg.dtype != torch.float32 or marg.device.type != "cuda" or not marg.is_contiguous():
+            raise ValueError("marg must be a contiguous float32 [b, v, o] tensor on the GPU")
+        b, v, o = marg.shape
+        dev = marg.device
+        if v > o:
+            raise ValueError("arc_confidence needs v <= o (got v %d, o %d)" % (v, o))
+        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
+            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
+        if pred.dtype != torch.int32 or pred.device != dev or tuple(pred.shape) != (b, v, 2) or not pred.is_contiguous():
+            raise ValueError("pred must be a contiguous int32 %s tensor on %s" % ([b, v, 2], dev))
+        conf = torch.empty(b, v, dtype=torch.float32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_arc_confidence(ctypes.byref(d), _ptr(marg), o, _ptr(n_nodes), _ptr(pred),
+                                                 _ptr(conf), _stream()), "ggnn_arc_confidence")
+        return conf
 
 
 def _tree_args(name, scores, n_nodes, pred, gold, counts):

@@ -33,7 +33,10 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
   spanning tree of the head scores (``ggnn_tree_decode``, ``csrc/k_tree.h``),
   with ``tree="projective"`` the heads of a graph that is not a projective
   tree by the best projective tree (``ggnn_projective_decode``,
-  ``csrc/k_proj.h``)
+  ``csrc/k_proj.h``), with ``tree="projective-mbr"`` the minimum Bayes risk
+  projective tree of the arc marginals (``ggnn_projective_marginals``,
+  ``csrc/k_marg.h``); ``confidence=True`` adds the marginal of every returned
+  head
 
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
@@ -78,13 +81,14 @@ KEEP_KEYS = ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weigh
 
 
 def _tree_mode(tree):
-    """The ``tree`` keyword of the decoding entries: False, True or
-    "projective" (returned as given); anything else is a ValueError."""
+    """The ``tree`` keyword of the decoding entries: False, True,
+    "projective" or "projective-mbr" (returned as given); anything else is a
+    ValueError."""
     if isinstance(tree, (bool, np.bool_)):
         return bool(tree)
-    if isinstance(tree, str) and tree == "projective":
+    if isinstance(tree, str) and tree in ("projective", "projective-mbr"):
         return tree
-    raise ValueError('tree must be False, True or "projective", got %r' % (tree,))
+    raise ValueError('tree must be False, True, "projective" or "projective-mbr", got %r' % (tree,))
 
 
 def mlp_init(shape, rng):
@@ -884,7 +888,9 @@ class DenseGGNNChemModel(BtbBatching):
         the maximum spanning tree before the counts are read (ggnn_tree_decode,
         as predict_batch(tree=True) returns them); tree="projective": by the
         best projective tree when they are not a projective tree
-        (ggnn_projective_decode).  Any other value of tree raises ValueError."""
+        (ggnn_projective_decode); tree="projective-mbr": by the minimum Bayes
+        risk projective tree (predict_batch).  Any other value of tree raises
+        ValueError."""
         if _tree_mode(tree) and not on_device:
             raise ValueError("evaluate_batch: tree=True needs on_device=True")
         if on_device:
@@ -973,7 +979,7 @@ class DenseGGNNChemModel(BtbBatching):
                 loss = self.build_loss()
         return loss
 
-    def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True):
+    def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False):
         """_eval_forward of a feed (default: the staged one) followed by the
         decode launch on the same stream.  Returns a dict: loss (scalar
         tensor), ph (the staged placeholders), b, v, n_nodes (host int32 [b],
@@ -984,14 +990,31 @@ class DenseGGNNChemModel(BtbBatching):
         [b] joins the dict; a graph with regular == 0 is not passed to it
         (node count 0) and gets status 2.  tree="projective": the projective
         pass (ggnn_projective_decode, the host form on a CPU device) takes the
-        MST pass's place, on the same scores and with the same status rules."""
-        projective = _tree_mode(tree) == "projective"
+        MST pass's place, on the same scores and with the same status rules.
+        tree="projective-mbr": after the decode the projective arc marginals of
+        the head probabilities (ggnn_projective_marginals on n * regular), the
+        decode again with the marginals in the head probabilities' place, and
+        the projective pass on the marginals' integer scores: the tree with
+        the most expected-correct heads.  'tree_status' is then 2 for a graph
+        that is not regular or has no marginals (it keeps its plain arg-max),
+        else the projective pass's own (0: the arg-max of the marginals was a
+        projective tree, 1: replaced by the MBR tree).  confidence (not with
+        tree=True): 'head_confidence' [b, v] float32, the marginal of every
+        returned head (ggnn_arc_confidence; for a graph without marginals the
+        head probability itself), and 'log_partition' [b] join the dict; the
+        marginals launch and the gather follow the other launches."""
+        mode = _tree_mode(tree)
+        projective, mbr = mode == "projective", mode == "projective-mbr"
+        if confidence and mode is True:
+            raise ValueError("confidence: a tree of tree=True may cross, it has no probability under the "
+                             "distribution over projective trees; use tree=False, \"projective\" or "
+                             "\"projective-mbr\"")
         loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
         ph = dict(self.placeholders)
         b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
         o, oe = self.params["output_size"], self.output_size_edges
         r = {"loss": loss.detach(), "ph": ph, "b": b, "v": v, "pred": None, "gold": None, "counts": None,
-             "tree_status": None}
+             "tree_status": None, "head_confidence": None, "log_partition": None}
         n = r["n_nodes"] = self._feed_n_nodes(ph)
         if n is None:
             return r
@@ -1003,8 +1026,21 @@ class DenseGGNNChemModel(BtbBatching):
                 y = np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o)
                 y_e = np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)
             r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(probs.numpy(), probs_e.numpy(), n, y, y_e)
-            if tree:
-                regular = r["counts"][:, 4] == 1
+            regular = r["counts"][:, 4] == 1
+            if mbr or confidence:
+                marg, logz, m_scores, m_status, _ = _eval.projective_marginals_arrays(
+                    probs.numpy(), np.where(regular, n, 0), single_root)
+                marg = marg.astype(np.float32)
+            if mbr:
+                r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(marg, probs_e.numpy(), n, y, y_e)
+                pred, counts, status = _eval.projective_decode_arrays(
+                    m_scores, np.where(regular, n, 0), r["pred"], single_root, r["gold"],
+                    r["counts"] if with_gold else None)
+                r["pred"] = pred
+                r["tree_status"] = np.where(regular & (m_status == 1), status, 2).astype(np.int32)
+                if with_gold:
+                    r["counts"] = counts
+            elif tree:
                 host_pass = _eval.projective_decode_arrays if projective else _eval.tree_decode_arrays
                 pred, counts, status = host_pass(
                     _eval.tree_scores(probs.numpy(), n, v), np.where(regular, n, 0), r["pred"], single_root,
@@ -1012,17 +1048,35 @@ class DenseGGNNChemModel(BtbBatching):
                 r["pred"], r["tree_status"] = pred, np.where(regular, status, 2).astype(np.int32)
                 if with_gold:
                     r["counts"] = counts
+            if confidence:
+                r["head_confidence"] = _eval.arc_confidence_arrays(marg, n, r["pred"])
+                r["log_partition"] = logz.astype(np.float32)
             return r
         n_dev = self._up_nodes(n, self.device)
-        r["pred"], r["gold"], r["counts"] = self._decode_heads().decode(
-            [probs, probs_e], n_dev, self._last_labels if with_gold else None)
-        if tree:
+        heads = self._decode_heads()
+        labels = self._last_labels if with_gold else None
+        r["pred"], r["gold"], r["counts"] = heads.decode([probs, probs_e], n_dev, labels)
+        if mbr:
             regular = r["counts"][:, 4] == 1
-            heads = self._decode_heads()
+            n_reg = (n_dev * regular).to(torch.int32)
+            marg, logz, m_scores, m_status = heads.projective_marginals(probs.contiguous(), n_reg, single_root)
+            r["pred"], r["gold"], r["counts"] = heads.decode([marg, probs_e], n_dev, labels)
+            status = heads.projective_decode(m_scores, n_reg, r["pred"], r["gold"],
+                                             r["counts"] if with_gold else None, single_root)
+            r["tree_status"] = torch.where(regular & (m_status == 1), status, torch.full_like(status, 2))
+        elif tree:
+            regular = r["counts"][:, 4] == 1
             status = (heads.projective_decode if projective else heads.tree_decode)(
                 tree_scores(probs, n_dev, v), (n_dev * regular).to(torch.int32), r["pred"], r["gold"],
                 r["counts"] if with_gold else None, single_root)
             r["tree_status"] = torch.where(regular, status, torch.full_like(status, 2))
+        if confidence:
+            if not mbr:
+                n_reg = (n_dev * (r["counts"][:, 4] == 1)).to(torch.int32)
+                marg, logz, _, _ = heads.projective_marginals(probs.contiguous(), n_reg, single_root,
+                                                              with_scores=False)
+            r["head_confidence"] = heads.arc_confidence(marg, n_dev, r["pred"])
+            r["log_partition"] = logz
         return r
 
     def _host_pred(self, ph, b, v):
@@ -1034,7 +1088,7 @@ class DenseGGNNChemModel(BtbBatching):
                                      np.asarray(ph["node_mask"], np.float32).reshape(b, v, o),
                                      np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
 
-    def predict_batch(self, feed_dict=None, tree=False, single_root=True):
+    def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False):
         """The predicted tree of every graph of a batch: {'heads': [b, v],
         'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
         arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
@@ -1052,9 +1106,23 @@ class DenseGGNNChemModel(BtbBatching):
         projective tree of the same scores instead (ggnn_projective_decode,
         Eisner's algorithm); the MST pass does not run, and 'tree_status' says
         0 = was a projective tree, 1 = repaired, 2 = no projective tree exists
-        / not attempted.  tree must be False, True or "projective"."""
+        / not attempted.  tree="projective-mbr": 'heads' hold the minimum
+        Bayes risk projective tree, the one with the most expected-correct
+        heads under the distribution over projective trees that the head
+        probabilities define (ggnn_projective_marginals, then
+        ggnn_projective_decode on the marginals' scores); 'tree_status' says 0
+        = the arg-max of the marginals was a projective tree, 1 = replaced by
+        the MBR tree, 2 = no projective tree / not attempted (the plain
+        arg-max).  confidence (with tree False, "projective" or
+        "projective-mbr"; ValueError with tree=True): the dict gains
+        'head_confidence' [b, v] float32, the projective marginal of every
+        returned head (0 where there is no prediction), and 'log_partition'
+        [b].  tree must be False, True, "projective" or "projective-mbr"."""
         tree = _tree_mode(tree)
-        r = self._decode_forward(feed_dict, False, tree, single_root)
+        if confidence and tree is True:
+            raise ValueError("predict_batch: confidence needs tree=False, \"projective\" or \"projective-mbr\" "
+                             "(a crossing tree has no probability under the projective distribution)")
+        r = self._decode_forward(feed_dict, False, tree, single_root, confidence)
         ph, b, v = r["ph"], r["b"], r["v"]
         pred = r["pred"]
         if pred is None:
@@ -1070,10 +1138,17 @@ class DenseGGNNChemModel(BtbBatching):
             status = np.full(b, 2, np.int32)
         elif isinstance(status, torch.Tensor):
             status = status.cpu().numpy()
-        return {"heads": np.ascontiguousarray(pred[:, :, 0]), "labels": np.ascontiguousarray(pred[:, :, 1]),
-                "n_nodes": n, "sentences_id": ph.get("sentences_id"), "tree_status": status}
+        out = {"heads": np.ascontiguousarray(pred[:, :, 0]), "labels": np.ascontiguousarray(pred[:, :, 1]),
+               "n_nodes": n, "sentences_id": ph.get("sentences_id"), "tree_status": status}
+        if confidence:
+            conf, logz = r["head_confidence"], r["log_partition"]
+            if conf is None:                 # masks not in closed form: no marginals
+                conf, logz = np.zeros((b, v), np.float32), np.full(b, np.nan, np.float32)
+            as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+            out["head_confidence"], out["log_partition"] = as_np(conf), as_np(logz)
+        return out
 
-    def parse(self, raw_data, tree=False, single_root=True):
+    def parse(self, raw_data, tree=False, single_root=True, confidence=False):
         """Parse raw btb sentences (the dicts process_raw_graphs accepts;
         'targets' may be absent): one entry per input sentence, in input
         order, in the JSON's own 'targets' form [[head, label], ...] for nodes
@@ -1083,8 +1158,14 @@ class DenseGGNNChemModel(BtbBatching):
         predict_batch(tree=True): every sentence for which a dependency tree
         exists comes back as one.  tree="projective": every sentence for which
         a projective dependency tree exists comes back as one (no crossing
-        arcs; predict_batch(tree="projective"))."""
+        arcs; predict_batch(tree="projective")).  tree="projective-mbr": the
+        minimum Bayes risk projective tree (predict_batch).  confidence:
+        returns (trees, confidences) with confidences[k] a list of floats
+        aligned with trees[k], the projective marginal of each returned head;
+        ValueError with tree=True."""
         tree = _tree_mode(tree)
+        if confidence and tree is True:
+            raise ValueError("parse: confidence needs tree=False, \"projective\" or \"projective-mbr\"")
         raw = []
         for k, d in enumerate(raw_data):
             c = dict(d)
@@ -1092,14 +1173,17 @@ class DenseGGNNChemModel(BtbBatching):
             c["id"] = k                      # (in the copy: the batches carry the input position)
             raw.append(c)
         out = [[] for _ in raw]
+        conf = [[] for _ in raw]
         data = self.process_raw_graphs(raw, False)
         for feed in self.make_minibatch_iterator(data, False):
-            p = self.predict_batch(feed, tree, single_root)
-            for k, heads, labels in zip(p["sentences_id"], p["heads"], p["labels"]):
+            p = self.predict_batch(feed, tree, single_root, confidence)
+            for g, (k, heads, labels) in enumerate(zip(p["sentences_id"], p["heads"], p["labels"])):
                 rg_h = [[int(x), 1] for x in heads[1:] if x >= 0]
                 rg_e = [[0, int(x) + 1] for x in labels[1:] if x >= 0]
                 out[k] = _eval.merge_head_and_edge_graph(rg_h, rg_e)
-        return out
+                if confidence:
+                    conf[k] = [float(c) for x, c in zip(heads[1:], p["head_confidence"][g, 1:]) if x >= 0]
+        return (out, conf) if confidence else out
 
     def score_epoch(self, data, tree=False, single_root=True):
         """The validation pass of run_epoch with the scoring on the device:
@@ -1116,7 +1200,10 @@ class DenseGGNNChemModel(BtbBatching):
         (a graph on the host fallback is scored from its arg-max lists).
         tree="projective": the same with the projective pass
         (ggnn_projective_decode) in the MST pass's place; the same keys count
-        the graphs it repaired and those without a projective tree."""
+        the graphs it repaired and those without a projective tree.
+        tree="projective-mbr": the MBR chain of predict_batch; the same bytes
+        are fetched, 'repaired_graphs' counts the graphs whose marginals'
+        arg-max was replaced by the MBR tree."""
         tree = _tree_mode(tree)
         stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0, "repaired_graphs": 0,
                                      "infeasible_graphs": 0}

@@ -504,6 +504,64 @@ int ggnn_projective_decode(const ggnn_dims* d,      /* b, v used */
                            int32_t* status,         /* device [b] out */
                            void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* Projective arc marginals: the sum-product twin of ggnn_projective_decode.
+ * The potential of "word i takes head j" in graph g is probs_head[g][i][j]
+ * where the arc is allowed (finite, > 0, 1 <= i < n, 0 <= j < n, j != i; n
+ * clamped as in ggnn_tree_decode); a projective dependency tree (ROOT
+ * leftmost, no crossing arcs, single_root: exactly one ROOT child) weighs the
+ * product of its words' potentials.
+ *   logz[g]       ln of the sum of the weights of all such trees
+ *   marg[g][i][j] the share of that sum held by the trees with the arc; 0 for
+ *                 an arc that is not allowed, for row 0, rows >= n and columns
+ *                 >= n.  Every word's row sums to 1, with single_root column 0
+ *                 sums to 1 (both up to fp32 rounding).
+ *   scores[g][i][j] (when not NULL) rint(marg * 2^20) for an allowed arc,
+ *                 GGNN_TREE_FORBIDDEN otherwise: the integer scores whose
+ *                 ggnn_projective_decode optimum is the minimum Bayes risk
+ *                 tree (most expected-correct heads); 2^20 * 255 < 2^30, so
+ *                 that call's range rule always holds.
+ *   status[g] = 1 the above was written
+ *   status[g] = 0 n < 2                       (logz = 0)
+ *   status[g] = 2 no projective tree exists over the allowed arcs, or ln Z is
+ *                 not finite                  (logz = -inf)
+ * For status != 1 marg[g] is a copy of probs_head[g] (all v rows) and
+ * scores[g] is GGNN_TREE_FORBIDDEN everywhere, so that everything downstream
+ * behaves as the plain arg-max for that graph.  marg must not alias probs_head.
+ * Inside and outside pass in log space, fp32, on ln p minus a per-word constant
+ * (the row's largest ln p, then ln Z' / (n - 1) of a first inside pass on top:
+ * the tables stay near 0; the marginals do not depend on the constants and
+ * logz gets their sum back).  Storage: a
+ * graph with n <= GGNN_MARG_LDS_MAXN keeps its seven triangular fp32 tables
+ * (14 n (n + 1) bytes) in LDS, a larger one in `workspace` (per graph; the
+ * tier follows the graph's n).  ggnn_projective_marginals_workspace_bytes(b,
+ * v) is 0 for v <= GGNN_MARG_LDS_MAXN and b * 14 * v * (v + 1) above; a
+ * smaller workspace is rejected.  Needs v <= o, v <= GGNN_TREE_MAXV, o <= 1024.
+ * One workgroup per graph, no atomics, every loop bounded by a function of n,
+ * every reduction in a fixed order.  Stream-ordered, allocation-free, legal
+ * under stream capture, bit-reproducible; booked under the heads kernel kind.
+ *
+ * ggnn_arc_confidence: conf[g][i] = marg[g][i][pred[g][i][0]], 0 where the
+ * predicted head is -1 (or >= o) or the row is 0 or >= n. */
+#define GGNN_MARG_LDS_MAXN 107
+size_t ggnn_projective_marginals_workspace_bytes(int32_t b, int32_t v);
+int ggnn_projective_marginals(const ggnn_dims* d,        /* b, v used */
+                              const float* probs_head,   /* device [b][v][o] */
+                              int32_t o,
+                              const int32_t* n_nodes,    /* device [b] */
+                              int32_t single_root,       /* 0 / 1 */
+                              float* marg,               /* device [b][v][o] out */
+                              float* logz,               /* device [b] out */
+                              int32_t* scores,           /* device [b][v][o] out, or NULL */
+                              int32_t* status,           /* device [b] out */
+                              void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+int ggnn_arc_confidence(const ggnn_dims* d,              /* b, v used */
+                        const float* marg,               /* device [b][v][o] */
+                        int32_t o,
+                        const int32_t* n_nodes,          /* device [b] */
+                        const int32_t* pred,             /* device [b][v][2] */
+                        float* conf,                     /* device [b][v] out */
+                        ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */

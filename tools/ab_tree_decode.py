@@ -28,6 +28,23 @@ tree's arcs, so every graph takes the projective fast path ("peaked"'s gold
 trees generally cross: there the arg-max is a non-projective tree, the MST
 pass takes its fast path and the projective pass repairs every graph with few
 changes).  --epoch then also scores the dev set with tree="projective".
+
+    python tools/ab_tree_decode.py --marginals [--epoch]
+
+alternates, in one process, the plain decode, decode + projective pass, the
+projective marginals alone (ggnn_projective_marginals with scores) and the
+whole MBR chain (decode, marginals, decode of the marginals, projective pass
+on their scores) on the same inputs; per line
+  decode_ms / decode_proj_ms / proj_ms   as above
+  marg_ms          ggnn_projective_marginals alone
+  mbr_ms           the MBR chain;  mbr_extra_ms = mbr_ms - decode_ms
+  mbr_status       graphs whose marginals' arg-max was a projective tree / was
+                   replaced by the MBR tree / without marginals
+  host_marg_ms     the fetch + evaluation.projective_marginals_arrays (float64;
+                   timed on the first 32 graphs and scaled to the batch)
+  marg_err         largest |marg - float64 host form| of the batch
+--epoch then scores the dev set with tree="projective" against
+tree="projective-mbr" (time, UAS, repaired graphs, fetched bytes).
 """
 import argparse
 import json
@@ -167,6 +184,79 @@ def kernel_sizes(torch, sizes, projective=False):
             print(json.dumps(out), flush=True)
 
 
+def marginals_sizes(torch, sizes):
+    from ggnn_amd import evaluation as E
+    from ggnn_amd.heads import OutputHeads, tree_scores
+    dev = torch.device("cuda", 0)
+    oh = OutputHeads(64)
+    for (b, v, o) in sizes:
+        for regime in ("flat", "peaked", "peaked-projective"):
+            ph, pe, n = batch(b, v, o, 46, regime, seed=b + v)
+            ph_d, pe_d, n_d = (torch.from_numpy(x).to(dev) for x in (ph, pe, n))
+            scores = tree_scores(ph_d, n_d, v)
+
+            def plain():
+                return oh.decode([ph_d, pe_d], n_d)
+
+            def with_proj():
+                pred, _, _ = oh.decode([ph_d, pe_d], n_d)
+                return pred, oh.projective_decode(scores, n_d, pred)
+
+            def marginals():
+                return oh.projective_marginals(ph_d, n_d, True)
+
+            def mbr():
+                oh.decode([ph_d, pe_d], n_d)
+                marg, _, m_scores, m_status = oh.projective_marginals(ph_d, n_d, True)
+                pred, _, _ = oh.decode([marg, pe_d], n_d)
+                return pred, oh.projective_decode(m_scores, n_d, pred), m_status
+
+            calls = 40 if b * v <= 2048 else 10
+            t = alternated(torch, [plain, with_proj, marginals, mbr], calls=calls)
+            out = {"b": b, "v": v, "o": o, "regime": regime}
+            for key, x in zip(("decode_ms", "decode_proj_ms", "marg_ms", "mbr_ms"), t):
+                out[key], out[key + "_min"], out[key + "_max"] = x
+            out["proj_ms"] = out["decode_proj_ms"] - out["decode_ms"]
+            out["mbr_extra_ms"] = out["mbr_ms"] - out["decode_ms"]
+            marg, logz, m_scores, m_status = marginals()
+            pred, status, _ = mbr()
+            torch.cuda.synchronize()
+            tm = time.perf_counter()
+            k = min(b, 32)                                            # (the float64 host form: the first 32 graphs)
+            h = E.projective_marginals_arrays(ph_d[:k].cpu().numpy(), n_d[:k].cpu().numpy(), True)
+            out["host_marg_ms"] = (time.perf_counter() - tm) * 1e3 * b / k
+            out["host_marg_graphs"] = k
+            assert np.array_equal(m_status[:k].cpu().numpy(), h[3])
+            out["marg_err"] = float(np.abs(marg[:k].cpu().numpy().astype(np.float64) - h[0]).max())
+            status = np.where(m_status.cpu().numpy() == 1, status.cpu().numpy(), 2)
+            out["mbr_status"] = [int((status == k).sum()) for k in (0, 1, 2)]
+            print(json.dumps(out), flush=True)
+
+
+def epoch_mbr(torch):
+    from ggnn_amd.batching import TRAIN_WITH_DEV, wsj_model_sizes
+    from ggnn_amd.model import DenseGGNNChemModel
+    m = DenseGGNNChemModel(params={"hidden_size": 128, "num_timesteps": 2, "batch_size": 20,
+                                   "compact_adjacency": True}, seed=0,
+                           embedding_sizes=dict(loc=32, pos=16, word=32, edge=16), **wsj_model_sizes())
+    data = m.load_data(TRAIN_WITH_DEV["train_file"], False)
+    paths = (("projective", {"tree": "projective"}), ("projective_mbr", {"tree": "projective-mbr"}))
+    for _, kw in paths:
+        m.score_epoch(data, **kw)                                     # both paths warm
+    out = {"what": "score_epoch, 1700 dev sentences, batch 20, untrained model", "projective_s": [],
+           "projective_mbr_s": []}
+    for _ in range(3):                                                # alternating
+        for key, kw in paths:
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            r = m.score_epoch(data, **kw)
+            torch.cuda.synchronize()
+            out[key + "_s"].append(round(time.perf_counter() - t, 4))
+            out[key + "_uas"] = r[2]
+            out[key + "_stats"] = dict(m.decode_stats)
+    print(json.dumps(out), flush=True)
+
+
 def epoch(torch, projective=False):
     from ggnn_amd import evaluation as E
     from ggnn_amd.batching import DATA_DIR, TRAIN_WITH_DEV, read_btb_json, wsj_model_sizes
@@ -224,12 +314,21 @@ def main():
     ap.add_argument("--epoch", action="store_true", help="also time score_epoch and check parse on the dev set")
     ap.add_argument("--projective", action="store_true",
                     help="alternate the MST pass with ggnn_projective_decode (and tree=\"projective\" with --epoch)")
+    ap.add_argument("--marginals", action="store_true",
+                    help="alternate the plain decode, the projective pass, ggnn_projective_marginals and the MBR "
+                         "chain (and tree=\"projective\" against tree=\"projective-mbr\" with --epoch)")
     ap.add_argument("--sizes", default="20x40x150,256x128x150")
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "ab_tree_decode.py needs a HIP device"
     print(json.dumps({"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}), flush=True)
-    kernel_sizes(torch, [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")], args.projective)
+    sizes = [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")]
+    if args.marginals:
+        marginals_sizes(torch, sizes)
+        if args.epoch:
+            epoch_mbr(torch)
+        return
+    kernel_sizes(torch, sizes, args.projective)
     if args.epoch:
         epoch(torch, args.projective)
 
