@@ -1728,21 +1728,40 @@ int ggnn_heads_backward_dev(const ggnn_dims* d, const ggnn_output_head* heads, i
   return heads_backward_impl(d, heads, nheads, hT, h0, 0.f, target_num, d_loss, ws, dhT, dh0, stream);
 }
 
+// What the decode entry points check alike, in the order they report it.  oe:
+// the label head's width (ggnn_heads_decode) or NULL; tree: a pass that takes
+// single_root and is bounded by GGNN_TREE_MAXV; null_arg: a required pointer
+// is NULL.
+static int decode_args(const std::string& name, const ggnn_dims* d, int32_t o, const int32_t* oe, bool tree,
+                       int32_t single_root, bool null_arg) {
+  const auto S = [](long x) { return std::to_string(x); };
+  if (!d) return fail(GGNN_EINVAL, name + ": dims is NULL");
+  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, name + ": b, v must be >= 1");
+  if (o < 1 || o > HEAD_MAXO || (oe && (*oe < 1 || *oe > HEAD_MAXO)))
+    return fail(GGNN_EINVAL, name + (oe ? ": o and oe" : ": o") + " must lie in 1.." + S(HEAD_MAXO) + " (got " + S(o) +
+                                 (oe ? ", " + S(*oe) : "") + ")");
+  if (d->v > o) return fail(GGNN_EINVAL, name + ": v " + S(d->v) + " > o " + S(o));
+  if (tree && d->v > GGNN_TREE_MAXV)
+    return fail(GGNN_EINVAL, name + ": v " + S(d->v) + " > GGNN_TREE_MAXV " + S(GGNN_TREE_MAXV));
+  if (tree && single_root != 0 && single_root != 1) return fail(GGNN_EINVAL, name + ": single_root must be 0 or 1");
+  if (null_arg) return fail(GGNN_EINVAL, name + ": NULL pointer");
+  return GGNN_OK;
+}
+static int decode_workspace(const std::string& name, size_t need, const void* workspace, size_t workspace_bytes) {
+  if (need && (!workspace || workspace_bytes < need))
+    return fail(GGNN_EINVAL, name + ": workspace of " + std::to_string(workspace ? workspace_bytes : 0) + " bytes, " +
+                                 std::to_string(need) + " needed");
+  return GGNN_OK;
+}
+
 // the heads' probabilities -> predicted (head, label) per node and the LAS /
 // UAS counts per graph (k_decode.h); booked under the heads kind
 static_assert(GGNN_DECODE_COUNTS == DECODE_COUNTS, "counts layout");
 int ggnn_heads_decode(const ggnn_dims* d, const float* probs_head, int32_t o, const float* probs_label, int32_t oe,
                       const float* gold_head, const float* gold_label, const int32_t* n_nodes, int32_t* pred,
                       int32_t* gold, int32_t* counts, ggnn_stream_t stream) {
-  if (!d) return fail(GGNN_EINVAL, "heads_decode: dims is NULL");
-  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "heads_decode: b, v must be >= 1");
-  if (o < 1 || o > HEAD_MAXO || oe < 1 || oe > HEAD_MAXO)
-    return fail(GGNN_EINVAL, "heads_decode: o and oe must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
-                                 std::to_string(o) + ", " + std::to_string(oe) + ")");
-  if (d->v > o)
-    return fail(GGNN_EINVAL, "heads_decode: v " + std::to_string(d->v) + " > o " + std::to_string(o));
-  if (!probs_head || !probs_label || !n_nodes || !pred || !counts)
-    return fail(GGNN_EINVAL, "heads_decode: NULL pointer");
+  const bool null_arg = !probs_head || !probs_label || !n_nodes || !pred || !counts;
+  if (int rc = decode_args("heads_decode", d, o, &oe, false, 0, null_arg)) return rc;
   if ((gold_head == nullptr) != (gold_label == nullptr))
     return fail(GGNN_EINVAL, "heads_decode: gold_head and gold_label must be given together (one is NULL)");
   hipStream_t s = (hipStream_t)stream;
@@ -1765,17 +1784,8 @@ size_t ggnn_tree_decode_workspace_bytes(int32_t, int32_t) { return 0; }
 int ggnn_tree_decode(const ggnn_dims* d, const int32_t* scores, int32_t o, const int32_t* n_nodes,
                      int32_t single_root, int32_t* pred, const int32_t* gold, int32_t* counts, int32_t* status,
                      void* /*workspace*/, size_t /*workspace_bytes*/, ggnn_stream_t stream) {
-  if (!d) return fail(GGNN_EINVAL, "tree_decode: dims is NULL");
-  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "tree_decode: b, v must be >= 1");
-  if (o < 1 || o > HEAD_MAXO)
-    return fail(GGNN_EINVAL, "tree_decode: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
-                                 std::to_string(o) + ")");
-  if (d->v > o) return fail(GGNN_EINVAL, "tree_decode: v " + std::to_string(d->v) + " > o " + std::to_string(o));
-  if (d->v > GGNN_TREE_MAXV)
-    return fail(GGNN_EINVAL, "tree_decode: v " + std::to_string(d->v) + " > GGNN_TREE_MAXV " +
-                                 std::to_string(GGNN_TREE_MAXV));
-  if (single_root != 0 && single_root != 1) return fail(GGNN_EINVAL, "tree_decode: single_root must be 0 or 1");
-  if (!scores || !n_nodes || !pred || !status) return fail(GGNN_EINVAL, "tree_decode: NULL pointer");
+  if (int rc = decode_args("tree_decode", d, o, nullptr, true, single_root, !scores || !n_nodes || !pred || !status))
+    return rc;
   if ((gold == nullptr) != (counts == nullptr))
     return fail(GGNN_EINVAL, "tree_decode: gold and counts must be given together (one is NULL)");
   hipStream_t s = (hipStream_t)stream;
@@ -1797,25 +1807,12 @@ size_t ggnn_projective_decode_workspace_bytes(int32_t b, int32_t v) {
 int ggnn_projective_decode(const ggnn_dims* d, const int32_t* scores, int32_t o, const int32_t* n_nodes,
                            int32_t single_root, int32_t* pred, const int32_t* gold, int32_t* counts,
                            int32_t* status, void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
-  if (!d) return fail(GGNN_EINVAL, "projective_decode: dims is NULL");
-  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "projective_decode: b, v must be >= 1");
-  if (o < 1 || o > HEAD_MAXO)
-    return fail(GGNN_EINVAL, "projective_decode: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
-                                 std::to_string(o) + ")");
-  if (d->v > o)
-    return fail(GGNN_EINVAL, "projective_decode: v " + std::to_string(d->v) + " > o " + std::to_string(o));
-  if (d->v > GGNN_TREE_MAXV)
-    return fail(GGNN_EINVAL, "projective_decode: v " + std::to_string(d->v) + " > GGNN_TREE_MAXV " +
-                                 std::to_string(GGNN_TREE_MAXV));
-  if (single_root != 0 && single_root != 1)
-    return fail(GGNN_EINVAL, "projective_decode: single_root must be 0 or 1");
-  if (!scores || !n_nodes || !pred || !status) return fail(GGNN_EINVAL, "projective_decode: NULL pointer");
+  const char* const name = "projective_decode";
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, !scores || !n_nodes || !pred || !status)) return rc;
   if ((gold == nullptr) != (counts == nullptr))
     return fail(GGNN_EINVAL, "projective_decode: gold and counts must be given together (one is NULL)");
   const size_t need = ggnn_projective_decode_workspace_bytes(d->b, d->v);
-  if (need && (!workspace || workspace_bytes < need))
-    return fail(GGNN_EINVAL, "projective_decode: workspace of " + std::to_string(workspace ? workspace_bytes : 0) +
-                                 " bytes, " + std::to_string(need) + " needed");
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
   hipStream_t s = (hipStream_t)stream;
   Prof p(K_HEADS, s);
   hipLaunchKernelGGL(k_projective_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
@@ -1838,26 +1835,12 @@ size_t ggnn_projective_marginals_workspace_bytes(int32_t b, int32_t v) {
 int ggnn_projective_marginals(const ggnn_dims* d, const float* probs_head, int32_t o, const int32_t* n_nodes,
                               int32_t single_root, float* marg, float* logz, int32_t* scores, int32_t* status,
                               void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
-  if (!d) return fail(GGNN_EINVAL, "projective_marginals: dims is NULL");
-  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "projective_marginals: b, v must be >= 1");
-  if (o < 1 || o > HEAD_MAXO)
-    return fail(GGNN_EINVAL, "projective_marginals: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
-                                 std::to_string(o) + ")");
-  if (d->v > o)
-    return fail(GGNN_EINVAL, "projective_marginals: v " + std::to_string(d->v) + " > o " + std::to_string(o));
-  if (d->v > GGNN_TREE_MAXV)
-    return fail(GGNN_EINVAL, "projective_marginals: v " + std::to_string(d->v) + " > GGNN_TREE_MAXV " +
-                                 std::to_string(GGNN_TREE_MAXV));
-  if (single_root != 0 && single_root != 1)
-    return fail(GGNN_EINVAL, "projective_marginals: single_root must be 0 or 1");
-  if (!probs_head || !n_nodes || !marg || !logz || !status)
-    return fail(GGNN_EINVAL, "projective_marginals: NULL pointer");
+  const char* const name = "projective_marginals";
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, !probs_head || !n_nodes || !marg || !logz || !status))
+    return rc;
   if (marg == probs_head) return fail(GGNN_EINVAL, "projective_marginals: marg must not alias probs_head");
   const size_t need = ggnn_projective_marginals_workspace_bytes(d->b, d->v);
-  if (need && (!workspace || workspace_bytes < need))
-    return fail(GGNN_EINVAL, "projective_marginals: workspace of " +
-                                 std::to_string(workspace ? workspace_bytes : 0) + " bytes, " + std::to_string(need) +
-                                 " needed");
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
   hipStream_t s = (hipStream_t)stream;
   Prof p(K_HEADS, s);
   hipLaunchKernelGGL(k_projective_marginals, dim3((unsigned)d->b), dim3(256), 0, s, probs_head, (int)o,
@@ -1868,13 +1851,7 @@ int ggnn_projective_marginals(const ggnn_dims* d, const float* probs_head, int32
 }
 int ggnn_arc_confidence(const ggnn_dims* d, const float* marg, int32_t o, const int32_t* n_nodes,
                         const int32_t* pred, float* conf, ggnn_stream_t stream) {
-  if (!d) return fail(GGNN_EINVAL, "arc_confidence: dims is NULL");
-  if (d->b < 1 || d->v < 1) return fail(GGNN_EINVAL, "arc_confidence: b, v must be >= 1");
-  if (o < 1 || o > HEAD_MAXO)
-    return fail(GGNN_EINVAL, "arc_confidence: o must lie in 1.." + std::to_string(HEAD_MAXO) + " (got " +
-                                 std::to_string(o) + ")");
-  if (d->v > o) return fail(GGNN_EINVAL, "arc_confidence: v " + std::to_string(d->v) + " > o " + std::to_string(o));
-  if (!marg || !n_nodes || !pred || !conf) return fail(GGNN_EINVAL, "arc_confidence: NULL pointer");
+  if (int rc = decode_args("arc_confidence", d, o, nullptr, false, 0, !marg || !n_nodes || !pred || !conf)) return rc;
   hipStream_t s = (hipStream_t)stream;
   Prof p(K_HEADS, s);
   hipLaunchKernelGGL(k_arc_confidence, dim3(grid1d((long)d->b * d->v)), dim3(256), 0, s, marg, (int)o,

@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(256) k_projective_marginals(const float* __res
                                                               float* __restrict__ logz, int* __restrict__ scores,
                                                               int* __restrict__ status, float* ws, long ws_stride) {
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = max(0, min(n_nodes[g], min(v, min(o, TREE_MAXV))));
+  const int n = tree_node_count(n_nodes[g], v, o);
   const long base = (long)g * v * o;
   const float* __restrict__ P = probs + base;
   __shared__ float tab[MARG_TABLES * PROJ_TRI(MARG_LDS_MAXN)];

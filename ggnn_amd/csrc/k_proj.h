@@ -212,50 +212,33 @@ __global__ void __launch_bounds__(256) k_projective_decode(const int* __restrict
                                                            int* __restrict__ counts, int* __restrict__ status,
                                                            int* ws, long ws_stride) {
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = max(0, min(n_nodes[g], min(v, min(o, TREE_MAXV))));
+  const int n = tree_node_count(n_nodes[g], v, o);
   const long base = (long)g * v;
   const int* __restrict__ S = scores + base * o;
   if (n < 2) {
     if (tid == 0) status[g] = 0;
     return;
   }
-  int K = 0;  // doublings: 2^K >= n
-  for (; K < 8 && (1 << K) < n; ++K) {
-  }
+  const int K = tree_doublings(n);
   __shared__ int tab[4 * PROJ_TRI(PROJ_LDS_MAXN)];
   __shared__ int jp[TREE_MAXV], alo[TREE_MAXV], ahi[TREE_MAXV], nh[TREE_MAXV], stk[PROJ_STACK], wmax[4], flag;
 
   // ---- the fast path: pred's heads already are a projective tree
-  int h = -1;
-  bool ok = tid == 0;
-  if (tid > 0 && tid < n) {
-    h = pred[(base + tid) * 2];
-    ok = h >= 0 && h < n && h != tid && S[(long)tid * o + h] != TREE_FORBIDDEN;
-  }
   const bool word = tid > 0 && tid < n;
-  if (tid < n) jp[tid] = ok ? h * (tid > 0) : tid;
-  alo[tid] = word && ok ? min(tid, h) : 0;
-  ahi[tid] = word && ok ? max(tid, h) : 0;
+  TreePred t = tree_pred_arc(pred, S, o, base, n, jp, tid);
+  alo[tid] = word && t.ok ? min(tid, t.h) : 0;
+  ahi[tid] = word && t.ok ? max(tid, t.h) : 0;
   nh[tid] = -1;
-  for (int s = 0; s < K; ++s) {
-    __syncthreads();
-    const int q = tid < n ? jp[jp[tid]] : 0;
-    __syncthreads();
-    if (tid < n) jp[tid] = q;
-  }
-  {
-    const int is_tree = __syncthreads_and(tid >= n || (ok && jp[tid] == 0));
-    const int roots = __syncthreads_count(word && ok && h == 0);
-    if (is_tree && (!single_root || roots == 1)) {
-      bool cross = false;
-      if (word) {
-        const int a = alo[tid], c = ahi[tid];
-        for (int j = 1; j < n; ++j) cross |= a < alo[j] && alo[j] < c && c < ahi[j];
-      }
-      if (!__syncthreads_or(cross)) {
-        if (tid == 0) status[g] = 0;
-        return;
-      }
+  tree_pred_follow(t, n, K, jp, tid);
+  if (t.is_tree && (!single_root || t.roots == 1)) {
+    bool cross = false;
+    if (word) {
+      const int a = alo[tid], c = ahi[tid];
+      for (int j = 1; j < n; ++j) cross |= a < alo[j] && alo[j] < c && c < ahi[j];
+    }
+    if (!__syncthreads_or(cross)) {
+      if (tid == 0) status[g] = 0;
+      return;
     }
   }
 
@@ -291,20 +274,5 @@ __global__ void __launch_bounds__(256) k_projective_decode(const int* __restrict
     if (word) pred[(base + tid) * 2] = nh[tid];
     if (tid == 0) status[g] = 1;
   }
-  // ---- las / uas of the repaired graph, by k_heads_decode's rule
-  if (gold && counts) {
-    bool hit_h = false, hit = false;
-    if (tid > 0 && tid < v) {
-      const long r = (base + tid) * 2;
-      const int g_h = gold[r], g_l = gold[r + 1];
-      const int p_h = tid < n ? nh[tid] : pred[r], p_l = pred[r + 1];
-      hit_h = g_h >= 0 && p_h == g_h;
-      hit = hit_h && p_l == g_l;
-    }
-    const int uas = __syncthreads_count(hit_h), las = __syncthreads_count(hit);
-    if (tid == 0) {
-      counts[(long)g * DECODE_COUNTS + 1] = las;
-      counts[(long)g * DECODE_COUNTS + 2] = uas;
-    }
-  }
+  tree_recount(gold, counts, pred, nh, n, v, base, g, tid);
 }

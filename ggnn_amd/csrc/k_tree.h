@@ -44,6 +44,66 @@
 #define TREE_NONE (-9223372036854775807LL - 1)
 #define TREE_ROOT_PENALTY (1LL << 42)
 
+// ---- shared by k_tree.h, k_proj.h and k_marg.h.  The whole workgroup calls
+// each helper and none returns past a barrier: a kernel's own early returns
+// follow the call, so every thread meets the same barriers.
+DEV int tree_node_count(int n_nodes_g, int v, int o) { return max(0, min(n_nodes_g, min(v, min(o, TREE_MAXV)))); }
+DEV int tree_doublings(int n) {  // K: 2^K >= n
+  int K = 0;
+  for (; K < 8 && (1 << K) < n; ++K) {
+  }
+  return K;
+}
+// The fast-path check "pred's heads already are a tree".  h: word tid's head
+// (-1 for ROOT and past n), ok: an allowed arc (true for ROOT), is_tree: every
+// word reaches ROOT, roots: ROOT's children.  tree_pred_arc fills h / ok and
+// seeds jp[0..n-1]; tree_pred_follow doubles jp K times and takes the votes.
+struct TreePred {
+  int h;
+  bool ok;
+  int is_tree, roots;
+};
+DEV TreePred tree_pred_arc(const int* __restrict__ pred, const int* __restrict__ S, int o, long base, int n, int* jp,
+                           int tid) {
+  TreePred t = {-1, tid == 0, 0, 0};
+  if (tid > 0 && tid < n) {
+    t.h = pred[(base + tid) * 2];
+    t.ok = t.h >= 0 && t.h < n && t.h != tid && S[(long)tid * o + t.h] != TREE_FORBIDDEN;
+  }
+  if (tid < n) jp[tid] = t.ok ? t.h * (tid > 0) : tid;
+  return t;
+}
+DEV void tree_pred_follow(TreePred& t, int n, int K, int* jp, int tid) {
+  for (int s = 0; s < K; ++s) {
+    __syncthreads();
+    const int q = tid < n ? jp[jp[tid]] : 0;
+    __syncthreads();
+    if (tid < n) jp[tid] = q;
+  }
+  t.is_tree = __syncthreads_and(tid >= n || (t.ok && jp[tid] == 0));
+  t.roots = __syncthreads_count(tid > 0 && tid < n && t.ok && t.h == 0);
+}
+// las / uas of the repaired graph g, by k_heads_decode's rule (nh: the new
+// heads of the words below n); gold and counts both or neither
+DEV void tree_recount(const int* __restrict__ gold, int* __restrict__ counts, const int* __restrict__ pred,
+                      const int* nh, int n, int v, long base, int g, int tid) {
+  if (gold && counts) {
+    bool hit_h = false, hit = false;
+    if (tid > 0 && tid < v) {
+      const long r = (base + tid) * 2;
+      const int g_h = gold[r], g_l = gold[r + 1];
+      const int p_h = tid < n ? nh[tid] : pred[r], p_l = pred[r + 1];
+      hit_h = g_h >= 0 && p_h == g_h;
+      hit = hit_h && p_l == g_l;
+    }
+    const int uas = __syncthreads_count(hit_h), las = __syncthreads_count(hit);
+    if (tid == 0) {
+      counts[(long)g * DECODE_COUNTS + 1] = las;
+      counts[(long)g * DECODE_COUNTS + 2] = uas;
+    }
+  }
+}
+
 // scores [b][v][o], n_nodes [b], pred [b][v][2] in/out, gold [b][v][2] and
 // counts [b][DECODE_COUNTS] both or neither, status [b].  grid = b, block = 256.
 __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ scores, int o,
@@ -51,16 +111,14 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
                                                      int* __restrict__ pred, const int* __restrict__ gold,
                                                      int* __restrict__ counts, int* __restrict__ status) {
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = max(0, min(n_nodes[g], min(v, min(o, TREE_MAXV))));
+  const int n = tree_node_count(n_nodes[g], v, o);
   const long base = (long)g * v;
   const int* __restrict__ S = scores + base * o;
   if (n < 2) {
     if (tid == 0) status[g] = 0;
     return;
   }
-  int K = 0;  // doublings: 2^K >= n
-  for (; K < 8 && (1 << K) < n; ++K) {
-  }
+  const int K = tree_doublings(n);
 
   // per word
   __shared__ int label[TREE_MAXV], dirty[TREE_MAXV], wsrc[TREE_MAXV], nh[TREE_MAXV];
@@ -72,26 +130,11 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
   __shared__ int wcnt[8];
 
   // ---- the fast path: pred's heads already are a tree
-  int h = -1;
-  bool ok = tid == 0;
-  if (tid > 0 && tid < n) {
-    h = pred[(base + tid) * 2];
-    ok = h >= 0 && h < n && h != tid && S[(long)tid * o + h] != TREE_FORBIDDEN;
-  }
-  if (tid < n) jp[tid] = ok ? h * (tid > 0) : tid;
-  for (int s = 0; s < K; ++s) {
-    __syncthreads();
-    const int q = tid < n ? jp[jp[tid]] : 0;
-    __syncthreads();
-    if (tid < n) jp[tid] = q;
-  }
-  {
-    const int is_tree = __syncthreads_and(tid >= n || (ok && jp[tid] == 0));
-    const int roots = __syncthreads_count(tid > 0 && tid < n && ok && h == 0);
-    if (is_tree && (!single_root || roots == 1)) {
-      if (tid == 0) status[g] = 0;
-      return;
-    }
+  TreePred t = tree_pred_arc(pred, S, o, base, n, jp, tid);
+  tree_pred_follow(t, n, K, jp, tid);
+  if (t.is_tree && (!single_root || t.roots == 1)) {
+    if (tid == 0) status[g] = 0;
+    return;
   }
 
   // ---- Chu-Liu/Edmonds
@@ -282,20 +325,5 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
     if (word) pred[(base + tid) * 2] = nh[tid];
     if (tid == 0) status[g] = 1;
   }
-  // ---- las / uas of the repaired graph, by k_heads_decode's rule
-  if (gold && counts) {
-    bool hit_h = false, hit = false;
-    if (tid > 0 && tid < v) {
-      const long r = (base + tid) * 2;
-      const int g_h = gold[r], g_l = gold[r + 1];
-      const int p_h = tid < n ? nh[tid] : pred[r], p_l = pred[r + 1];
-      hit_h = g_h >= 0 && p_h == g_h;
-      hit = hit_h && p_l == g_l;
-    }
-    const int uas = __syncthreads_count(hit_h), las = __syncthreads_count(hit);
-    if (tid == 0) {
-      counts[(long)g * DECODE_COUNTS + 1] = las;
-      counts[(long)g * DECODE_COUNTS + 2] = uas;
-    }
-  }
+  tree_recount(gold, counts, pred, nh, n, v, base, g, tid);
 }

@@ -1,0 +1,329 @@
+"""Decoding: the chain decode -> marginals -> tree / projective pass ->
+confidences, written once against a backend with the device binding's five
+methods (``decode``, ``tree_decode``, ``projective_decode``,
+``projective_marginals``, ``arc_confidence``): heads.OutputHeads on the GPU,
+``HostDecoder`` over evaluation.*_arrays for a model on a CPU device; and the
+model's decoding entries (``DecodingMixin``)."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import evaluation as _eval
+from .heads import tree_scores
+
+KEEP_KEYS = ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weight_dropout_keep_prob",
+             "emb_dropout_keep_prob")
+_NO_CONFIDENCE = {      # confidence with tree=True, in each entry's words
+    "_decode_forward": "confidence: a tree of tree=True may cross, it has no probability under the distribution "
+                       "over projective trees; use tree=False, \"projective\" or \"projective-mbr\"",
+    "predict_batch": "predict_batch: confidence needs tree=False, \"projective\" or \"projective-mbr\" "
+                     "(a crossing tree has no probability under the projective distribution)",
+    "parse": "parse: confidence needs tree=False, \"projective\" or \"projective-mbr\""}
+
+
+def _tree_mode(tree, confidence=False, caller=None):
+    """The ``tree`` keyword of the decoding entries: False, True,
+    "projective" or "projective-mbr" (returned as given); anything else is a
+    ValueError, and so is ``confidence`` with tree=True (``caller``'s text)."""
+    if isinstance(tree, (bool, np.bool_)):
+        if tree and confidence:
+            raise ValueError(_NO_CONFIDENCE[caller])
+        return bool(tree)
+    if isinstance(tree, str) and tree in ("projective", "projective-mbr"):
+        return tree
+    raise ValueError('tree must be False, True, "projective" or "projective-mbr", got %r' % (tree,))
+
+
+def _as_np(t):
+    return t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+
+
+def _in_place(host_form):
+    """A tree / projective pass with OutputHeads' signature over its host
+    form: pred and counts are updated in place (the host form returns copies)."""
+    def run(self, scores, n_nodes, pred, gold=None, counts=None, single_root=True):
+        new_pred, new_counts, status = host_form(scores, n_nodes, pred, single_root, gold, counts)
+        pred[...] = new_pred
+        if counts is not None:
+            counts[...] = new_counts
+        return status
+    return run
+
+
+class HostDecoder:
+    """OutputHeads' five decoding methods over the host forms, numpy in and
+    out; the marginals as float32, without the host form's span_max."""
+    tree_decode = _in_place(_eval.tree_decode_arrays)
+    projective_decode = _in_place(_eval.projective_decode_arrays)
+
+    def decode(self, probs, n_nodes, labels=None):
+        return _eval.decode_arrays(probs[0], probs[1], n_nodes, *(labels or (None, None)))
+
+    def projective_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True):
+        marg, logz, scores, status, _ = _eval.projective_marginals_arrays(probs_head, n_nodes, single_root)
+        return marg.astype(np.float32), logz.astype(np.float32), scores if with_scores else None, status
+
+    def arc_confidence(self, marg, n_nodes, pred):
+        return _eval.arc_confidence_arrays(marg, n_nodes, pred)
+
+
+def _select(keep, x, fill):
+    """x where keep, ``fill`` elsewhere: int32, in x's own array type."""
+    if isinstance(x, torch.Tensor):
+        return torch.where(keep, x, torch.full_like(x, fill))
+    return np.where(keep, x, fill).astype(np.int32)
+
+
+def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=True, confidence=False):
+    """The decode and what follows it, in launch order and in ``backend``'s
+    array type (probs [b, v, o], probs_e [b, v, oe] float32, n_nodes int32
+    [b], labels: the two heads' targets or None).  mode True / "projective":
+    the MST / projective pass on tree_scores of probs; "projective-mbr": the
+    marginals of probs, the decode again with them in probs' place, the
+    projective pass on their integer scores; confidence: the marginals (unless
+    MBR made them) and the gather of the returned heads' marginals come last.
+    The passes and the marginals see n * regular; tree_status is the pass's own
+    where a graph is regular (MBR: and has marginals), 2 elsewhere."""
+    on_device, mbr = isinstance(probs, torch.Tensor), mode == "projective-mbr"
+    pred, gold, counts = backend.decode([probs, probs_e], n_nodes, labels)
+    regular = counts[:, 4] == 1
+    n_reg = _select(regular, n_nodes, 0) if mode or confidence else None
+    if mbr:
+        marg, logz, scores, has_marg = backend.projective_marginals(probs, n_reg, single_root)
+        pred, gold, counts = backend.decode([marg, probs_e], n_nodes, labels)
+        regular = regular & (has_marg == 1)
+    elif mode:
+        scores = (tree_scores if on_device else _eval.tree_scores)(probs, n_nodes, probs.shape[1])
+    out = {"pred": pred, "gold": gold, "counts": counts, "tree_status": None}
+    if mode:
+        run = backend.tree_decode if mode is True else backend.projective_decode
+        status = run(scores, n_reg, pred, gold, None if gold is None else counts, single_root)
+        out["tree_status"] = _select(regular, status, 2)
+    if confidence:
+        if not mbr:     # (nothing reads the integer scores)
+            marg, logz, _, _ = backend.projective_marginals(probs, n_reg, single_root, with_scores=False)
+        out["head_confidence"], out["log_partition"] = backend.arc_confidence(marg, n_nodes, pred), logz
+    return out
+
+
+class DecodingMixin:
+    """DenseGGNNChemModel's decoding entries (ggnn_heads_decode and after)."""
+
+    def _feed_n_nodes(self, ph):
+        """The graphs' node counts of a feed (node_mask_edges row sums /
+        output_size_edges) as int32 [b], or None when the feed's masks are not
+        of get_mask's closed form (the decode kernel rebuilds them from the
+        counts alone)."""
+        b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
+        o, oe = self.params["output_size"], self.output_size_edges
+        if v > o or ph.get("node_mask") is None or ph.get("node_mask_edges") is None:
+            return None
+        m = np.asarray(ph["node_mask"]).reshape(b, v, o)
+        m_e = np.asarray(ph["node_mask_edges"]).reshape(b, v, oe)
+        n = np.rint(m_e.sum(axis=(1, 2)) / oe).astype(np.int32)
+        ref, ref_e = _eval.closed_form_masks(n, v, o, oe)
+        if not (np.array_equal(m, ref) and np.array_equal(m_e, ref_e)):
+            return None
+        return n
+
+    def _eval_forward(self, feed):
+        """The dropout-free forward of a feed (a copy of it with the four keep
+        probabilities at 1.0 is staged): through its shape's captured step
+        when _graph_ok, else build_loss on the eager path.  Returns the loss."""
+        feed = dict(feed)
+        feed.update((k, 1.0) for k in KEEP_KEYS)
+        with torch.no_grad():
+            loss = self._graph_step(feed, False) if self._graph_ok(feed) else None
+            if loss is None:
+                self.graph_stats["eager"] += 1
+                self.feed(feed)
+                loss = self.build_loss()
+        return loss
+
+    def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False):
+        """_eval_forward of a feed (default: the staged one), then decode_chain
+        eagerly on the same stream (never inside a captured step).  Returns a
+        dict: loss (scalar tensor), ph (the staged placeholders), b, v, n_nodes
+        (host int32 [b], None: masks not in closed form) and the chain's pred /
+        gold / counts / tree_status / head_confidence / log_partition: device
+        tensors, numpy arrays on a CPU device (HostDecoder), None without
+        n_nodes or where tree / confidence (predict_batch's) do not ask."""
+        mode = _tree_mode(tree, confidence, "_decode_forward")
+        loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
+        ph = dict(self.placeholders)
+        b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
+        o, oe = self.params["output_size"], self.output_size_edges
+        r = {"loss": loss.detach(), "ph": ph, "b": b, "v": v, "pred": None, "gold": None, "counts": None,
+             "tree_status": None, "head_confidence": None, "log_partition": None}
+        n = r["n_nodes"] = self._feed_n_nodes(ph)
+        if n is None:
+            return r
+        probs = self.ops["computed_values"].detach().reshape(b, v, o).contiguous()
+        probs_e = self.ops["computed_values_edges"].detach().reshape(b, v, oe)
+        if probs.device.type == "cuda":
+            backend, n, labels = self._decode_heads(), self._up_nodes(n, self.device), self._last_labels
+        else:
+            backend, probs, probs_e = HostDecoder(), probs.numpy(), probs_e.numpy()
+            labels = [np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o),
+                      np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)] if with_gold else None
+        r.update(decode_chain(backend, probs, probs_e, n, labels if with_gold else None, mode, single_root, confidence))
+        return r
+
+    def _host_pred(self, ph, b, v):
+        """pred [b, v, 2] of the staged batch from its fetched probabilities and
+        the feed's own masks (a feed whose masks the decode cannot rebuild)."""
+        o, oe = self.params["output_size"], self.output_size_edges
+        return _eval.pred_from_masks(self.ops["computed_values"].detach().cpu().numpy(),
+                                     self.ops["computed_values_edges"].detach().cpu().numpy(),
+                                     np.asarray(ph["node_mask"], np.float32).reshape(b, v, o),
+                                     np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
+
+    def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False):
+        """The predicted tree of every graph of a batch: {'heads': [b, v],
+        'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
+        arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
+        prediction: node 0, padding, an all-zero row), 'n_nodes': [b],
+        'sentences_id', 'tree_status'}.  Runs the dropout-free forward and
+        decodes on the device; 2 * b * v int32 come back instead of both
+        probability arrays.  tree: 'heads' of a graph whose arg-max heads are
+        not a dependency tree (single_root: with one ROOT child) hold the
+        maximum spanning tree of the head scores instead (ggnn_tree_decode on
+        tree_scores of the head probabilities) and 'tree_status' [b] int32
+        says 0 = was a tree, 1 = repaired, 2 = no tree exists / not attempted
+        (left as the arg-max); None without tree.  tree="projective": 'heads'
+        of a graph whose arg-max heads are not a PROJECTIVE dependency tree
+        (no two arcs cross, ROOT at the leftmost position) hold the best
+        projective tree of the same scores instead (ggnn_projective_decode,
+        Eisner's algorithm); the MST pass does not run, and 'tree_status' says
+        0 = was a projective tree, 1 = repaired, 2 = no projective tree exists
+        / not attempted.  tree="projective-mbr": 'heads' hold the minimum
+        Bayes risk projective tree, the one with the most expected-correct
+        heads under the distribution over projective trees that the head
+        probabilities define (ggnn_projective_marginals, then
+        ggnn_projective_decode on the marginals' scores); 'tree_status' says 0
+        = the arg-max of the marginals was a projective tree, 1 = replaced by
+        the MBR tree, 2 = no projective tree / not attempted (the plain
+        arg-max).  confidence (with tree False, "projective" or
+        "projective-mbr"; ValueError with tree=True): the dict gains
+        'head_confidence' [b, v] float32, the projective marginal of every
+        returned head (0 where there is no prediction), and 'log_partition'
+        [b].  tree must be False, True, "projective" or "projective-mbr"."""
+        tree = _tree_mode(tree, confidence, "predict_batch")
+        r = self._decode_forward(feed_dict, False, tree, single_root, confidence)
+        ph, b, v, pred = r["ph"], r["b"], r["v"], r["pred"]
+        if pred is None:
+            pred = self._host_pred(ph, b, v)
+            n = np.rint(np.asarray(ph["node_mask_edges"]).reshape(b, -1).sum(axis=1)
+                        / self.output_size_edges).astype(np.int32)
+        else:
+            n, pred = r["n_nodes"], _as_np(pred)
+        status = _as_np(r["tree_status"])
+        if tree and status is None:          # masks not in closed form: the repair is not attempted
+            status = np.full(b, 2, np.int32)
+        out = {"heads": np.ascontiguousarray(pred[:, :, 0]), "labels": np.ascontiguousarray(pred[:, :, 1]),
+               "n_nodes": n, "sentences_id": ph.get("sentences_id"), "tree_status": status}
+        if confidence:
+            conf, logz = r["head_confidence"], r["log_partition"]
+            if conf is None:                 # masks not in closed form: no marginals
+                conf, logz = np.zeros((b, v), np.float32), np.full(b, np.nan, np.float32)
+            out["head_confidence"], out["log_partition"] = _as_np(conf), _as_np(logz)
+        return out
+
+    def parse(self, raw_data, tree=False, single_root=True, confidence=False):
+        """Parse raw btb sentences (the dicts process_raw_graphs accepts;
+        'targets' may be absent): one entry per input sentence, in input
+        order, in the JSON's own 'targets' form [[head, label], ...] for nodes
+        1..n-1 with the label one-based -- what adj_mat_to_target(...,
+        is_probability=True) + merge_head_and_edge_graph give for the sentence.
+        A sentence process_raw_graphs drops (empty graph) yields [].  tree: as
+        predict_batch(tree=True): every sentence for which a dependency tree
+        exists comes back as one.  tree="projective": every sentence for which
+        a projective dependency tree exists comes back as one (no crossing
+        arcs; predict_batch(tree="projective")).  tree="projective-mbr": the
+        minimum Bayes risk projective tree (predict_batch).  confidence:
+        returns (trees, confidences) with confidences[k] a list of floats
+        aligned with trees[k], the projective marginal of each returned head;
+        ValueError with tree=True."""
+        tree = _tree_mode(tree, confidence, "parse")
+        # (copies: the batches carry the input position as 'id')
+        raw = [{"targets": [], **d, "id": k} for k, d in enumerate(raw_data)]
+        out, conf = [[] for _ in raw], [[] for _ in raw]
+        data = self.process_raw_graphs(raw, False)
+        for feed in self.make_minibatch_iterator(data, False):
+            p = self.predict_batch(feed, tree, single_root, confidence)
+            for g, (k, heads, labels) in enumerate(zip(p["sentences_id"], p["heads"], p["labels"])):
+                rg_h = [[int(x), 1] for x in heads[1:] if x >= 0]
+                rg_e = [[0, int(x) + 1] for x in labels[1:] if x >= 0]
+                out[k] = _eval.merge_head_and_edge_graph(rg_h, rg_e)
+                if confidence:
+                    conf[k] = [float(c) for x, c in zip(heads[1:], p["head_confidence"][g, 1:]) if x >= 0]
+        return (out, conf) if confidence else out
+
+    def score_epoch(self, data, tree=False, single_root=True):
+        """The validation pass of run_epoch with the scoring on the device:
+        per batch only the loss and the decode's counts [b, 5] are fetched
+        (pred / gold too for a batch with an irregular graph, scored through
+        the reference's lists; both probability arrays only for a feed whose
+        masks are not in closed form).  One batch in flight and the sums over
+        the ranks as in run_epoch.  Returns (loss, las, uas, label_acc,
+        instances_per_sec, steps) -- run_epoch's values.  ``decode_stats``
+        holds the pass's graphs, host-fallback graphs and fetched bytes.  tree:
+        the scores are those of the tree-constrained heads (ggnn_tree_decode
+        after the decode, its status [b] fetched beside the counts);
+        ``decode_stats`` counts the repaired graphs and those without a tree
+        (a graph on the host fallback is scored from its arg-max lists).
+        tree="projective": the same with the projective pass
+        (ggnn_projective_decode) in the MST pass's place; the same keys count
+        the graphs it repaired and those without a projective tree.
+        tree="projective-mbr": the MBR chain of predict_batch; the same bytes
+        are fetched, 'repaired_graphs' counts the graphs whose marginals'
+        arg-max was replaced by the MBR tree."""
+        tree = _tree_mode(tree)
+        stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0, "repaired_graphs": 0,
+                                     "infeasible_graphs": 0}
+        keys = ("counts", "tree_status") if tree else ("counts",)     # what a batch's scoring fetches
+
+        def step(feed, all_reduce):
+            r = self._decode_forward(feed, True, tree, single_root)
+            r["event"] = None
+            if r["counts"] is None:          # the host scorer decides: fetch what it reads
+                r["scored"] = self._score_batch()[:3]
+                r["host"] = [r["loss"].cpu()]
+                stats["d2h_bytes"] += 4 + 4 * r["b"] * r["v"] * (self.params["output_size"] + self.output_size_edges)
+                stats["fallback_graphs"] += r["b"]
+            elif isinstance(r["counts"], np.ndarray):   # a CPU device: HostDecoder's arrays
+                r["host"] = [r["loss"].reshape(1)] + [torch.from_numpy(r[k]) for k in keys]
+            else:
+                dev = [r["loss"].reshape(1)] + [r[k] for k in keys]
+                r["host"], r["event"] = self._fetch_counts.fetch(dev)
+                stats["d2h_bytes"] += sum(t.numel() * t.element_size() for t in dev)
+            return r
+
+        def consume(r):
+            batch_loss = float(r["host"][0].sum())
+            if r["counts"] is None:
+                scores = r["scored"]
+                if tree:
+                    stats["infeasible_graphs"] += r["b"]
+            else:
+                if tree:
+                    status = r["host"][2].numpy()
+                    stats["repaired_graphs"] += int((status == 1).sum())
+                    stats["infeasible_graphs"] += int((status == 2).sum())
+                lists = {}
+
+                def fallback(i):
+                    if not lists:
+                        lists["pred"], lists["gold"] = _as_np(r["pred"]), _as_np(r["gold"])
+                        if isinstance(r["pred"], torch.Tensor):
+                            stats["d2h_bytes"] += 2 * lists["pred"].nbytes
+                    stats["fallback_graphs"] += 1
+                    return _eval.graph_scores_from_lists(lists["pred"][i], lists["gold"][i])
+
+                scores = _eval.scores_from_counts(r["host"][1].numpy(), fallback)
+            stats["graphs"] += r["b"]
+            return (r["b"], batch_loss) + tuple(scores)
+
+        processed, loss, las, uas, uas_e, steps, _, elapsed = self._epoch(data, False, step, consume)
+        return loss / processed, las / processed, uas / processed, uas_e / processed, processed / elapsed, steps

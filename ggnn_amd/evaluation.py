@@ -165,6 +165,14 @@ def pred_from_masks(probs, probs_e, mask, mask_e):
                            np.asarray(probs_e, np.float32).reshape(m_e.shape) * m_e)
 
 
+def _node_counts(n_nodes, b, v, o):
+    """n_nodes as int64 [b], clipped to 0..min(v, o) as the kernels clip it."""
+    n = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
+    if n.shape[0] != b:
+        raise ValueError("n_nodes: %d values for %d graphs" % (n.shape[0], b))
+    return n
+
+
 def decode_arrays(probs, probs_e, n_nodes, labels=None, labels_e=None):
     """The host form of ``ggnn_heads_decode`` (include/ggnn.h), written with
     the scorer's own ``_first_max``: probs [b, v, o] and probs_e [b, v, e] are
@@ -181,9 +189,7 @@ def decode_arrays(probs, probs_e, n_nodes, labels=None, labels_e=None):
         raise ValueError("probs [b, v, o] and probs_e [b, v, e] expected, got %s and %s" % (p.shape, pe.shape))
     b, v, o = p.shape
     e = pe.shape[2]
-    n = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
-    if n.shape[0] != b:
-        raise ValueError("n_nodes: %d values for %d graphs" % (n.shape[0], b))
+    n = _node_counts(n_nodes, b, v, o)
     m, m_e = closed_form_masks(n, v, o, e)
     with np.errstate(invalid="ignore"):     # (inf * 0: a NaN, as on the reference's path)
         res, res_e = p * m.astype(np.float32), pe * m_e.astype(np.float32)
@@ -458,6 +464,46 @@ def _max_arborescence(s, n, single_root):
     return heads, levels
 
 
+def _repair_arrays(what, fine, solve, scores, n_nodes, pred, gold, counts):
+    """What tree_decode_arrays and projective_decode_arrays share: the
+    argument checks, the copies, the per-graph loop, the status and the
+    recount.  ``fine(scores[g], n, heads)``: the graph's heads are left alone
+    (status 0); else ``solve(scores[g], n)`` gives its new heads (status 1) or
+    None (status 2)."""
+    s = np.asarray(scores)
+    if s.ndim != 3 or s.dtype != np.int32:
+        raise ValueError("scores must be int32 [b, v, o]")
+    b, v, o = s.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("%s decode needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (what, TREE_MAXV, v, o))
+    pred = np.array(pred, np.int32)
+    if pred.shape != (b, v, 2):
+        raise ValueError("pred must be [%d, %d, 2]" % (b, v))
+    if (gold is None) != (counts is None):
+        raise ValueError("gold and counts are given together")
+    if counts is not None:
+        counts = np.array(counts, np.int32)
+        gold = np.asarray(gold)
+    nn = _node_counts(n_nodes, b, v, o)
+    status = np.zeros(b, np.int32)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2 or fine(s[g], n, pred[g, :, 0]):
+            continue
+        heads = solve(s[g], n)
+        if heads is None:
+            status[g] = 2
+            continue
+        status[g] = 1
+        pred[g, 1:n, 0] = heads[1:]
+        if counts is not None:
+            has = gold[g, 1:, 0] >= 0
+            hit_h = has & (pred[g, 1:, 0] == gold[g, 1:, 0])
+            counts[g, 1] = int((hit_h & (pred[g, 1:, 1] == gold[g, 1:, 1])).sum())
+            counts[g, 2] = int(hit_h.sum())
+    return pred, counts, status
+
+
 def tree_decode_arrays(scores, n_nodes, pred, single_root=True, gold=None, counts=None, levels=None):
     """The host form of ``ggnn_tree_decode`` (include/ggnn.h).  scores int32
     [b, v, o], n_nodes [b], pred int32 [b, v, 2] (decode_arrays'), gold
@@ -467,44 +513,19 @@ def tree_decode_arrays(scores, n_nodes, pred, single_root=True, gold=None, count
     its las / uas counts recounted; status 0 = already a tree, 2 = no tree
     exists; those graphs are returned as passed in.  ``levels``: a list that
     receives per graph the nesting depth of the contractions it needed."""
-    s = np.asarray(scores)
-    if s.ndim != 3 or s.dtype != np.int32:
-        raise ValueError("scores must be int32 [b, v, o]")
-    b, v, o = s.shape
-    if v > o or v > TREE_MAXV or o > 1024:
-        raise ValueError("tree decode needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
-    pred = np.array(pred, np.int32)
-    if pred.shape != (b, v, 2):
-        raise ValueError("pred must be [%d, %d, 2]" % (b, v))
-    if (gold is None) != (counts is None):
-        raise ValueError("gold and counts are given together")
-    if counts is not None:
-        counts = np.array(counts, np.int32)
-        gold = np.asarray(gold)
-    nn = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
-    if nn.shape[0] != b:
-        raise ValueError("n_nodes: %d values for %d graphs" % (nn.shape[0], b))
-    status = np.zeros(b, np.int32)
+    depths = []                  # of the graphs that were solved, in graph order
+
+    def solve(sg, n):
+        heads, lv = _max_arborescence(sg, n, single_root)
+        depths.append(lv)
+        return heads
+
+    out = _repair_arrays("tree", lambda sg, n, heads: is_tree(heads, n, single_root, sg), solve, scores, n_nodes,
+                         pred, gold, counts)
     if levels is not None:
-        del levels[:]
-    for g in range(b):
-        n = int(nn[g])
-        lv = 0
-        if n >= 2 and not is_tree(pred[g, :, 0], n, single_root, s[g]):
-            heads, lv = _max_arborescence(s[g], n, single_root)
-            if heads is None:
-                status[g] = 2
-            else:
-                status[g] = 1
-                pred[g, 1:n, 0] = heads[1:]
-                if counts is not None:
-                    has = gold[g, 1:, 0] >= 0
-                    hit_h = has & (pred[g, 1:, 0] == gold[g, 1:, 0])
-                    counts[g, 1] = int((hit_h & (pred[g, 1:, 1] == gold[g, 1:, 1])).sum())
-                    counts[g, 2] = int(hit_h.sum())
-        if levels is not None:
-            levels.append(lv)
-    return pred, counts, status
+        solved = iter(depths)
+        levels[:] = [next(solved) if st else 0 for st in out[2]]
+    return out
 
 
 # -------------------------------------------------------- projective decoding
@@ -615,45 +636,17 @@ def projective_decode_arrays(scores, n_nodes, pred, single_root=True, gold=None,
     uas recounted; status 0 = already a projective tree (or n < 2), 2 = S *
     (n - 1) >= 2^30 for the largest absolute allowed score S, or no projective
     tree exists; those graphs are returned as passed in."""
-    s = np.asarray(scores)
-    if s.ndim != 3 or s.dtype != np.int32:
-        raise ValueError("scores must be int32 [b, v, o]")
-    b, v, o = s.shape
-    if v > o or v > TREE_MAXV or o > 1024:
-        raise ValueError("projective decode needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
-    pred = np.array(pred, np.int32)
-    if pred.shape != (b, v, 2):
-        raise ValueError("pred must be [%d, %d, 2]" % (b, v))
-    if (gold is None) != (counts is None):
-        raise ValueError("gold and counts are given together")
-    if counts is not None:
-        counts = np.array(counts, np.int32)
-        gold = np.asarray(gold)
-    nn = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
-    if nn.shape[0] != b:
-        raise ValueError("n_nodes: %d values for %d graphs" % (nn.shape[0], b))
-    status = np.zeros(b, np.int32)
-    for g in range(b):
-        n = int(nn[g])
-        if n < 2 or (is_tree(pred[g, :, 0], n, single_root, s[g]) and is_projective(pred[g, :, 0], n)):
-            continue
-        a = s[g, 1:n, :n].astype(np.int64)
+    def solve(sg, n):
+        a = sg[1:n, :n].astype(np.int64)
         live = a != TREE_FORBIDDEN
         live[np.arange(n - 1), np.arange(1, n)] = False
-        heads = None
-        if int(np.abs(a[live]).max(initial=0)) * (n - 1) < 2 ** 30:
-            heads = _eisner(s[g], n, single_root)
-        if heads is None:
-            status[g] = 2
-            continue
-        status[g] = 1
-        pred[g, 1:n, 0] = heads[1:]
-        if counts is not None:
-            has = gold[g, 1:, 0] >= 0
-            hit_h = has & (pred[g, 1:, 0] == gold[g, 1:, 0])
-            counts[g, 1] = int((hit_h & (pred[g, 1:, 1] == gold[g, 1:, 1])).sum())
-            counts[g, 2] = int(hit_h.sum())
-    return pred, counts, status
+        if int(np.abs(a[live]).max(initial=0)) * (n - 1) >= 2 ** 30:      # the range rule
+            return None
+        return _eisner(sg, n, single_root)
+
+    return _repair_arrays("projective",
+                          lambda sg, n, heads: is_tree(heads, n, single_root, sg) and is_projective(heads, n),
+                          solve, scores, n_nodes, pred, gold, counts)
 
 
 def random_projective_heads(n, rng):
@@ -810,9 +803,7 @@ def projective_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.
     if v > o or v > TREE_MAXV or o > 1024:
         raise ValueError("projective marginals need v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
     dt = np.dtype(dtype)
-    nn = np.clip(np.asarray(n_nodes).astype(np.int64).reshape(-1), 0, min(v, o))
-    if nn.shape[0] != b:
-        raise ValueError("n_nodes: %d values for %d graphs" % (nn.shape[0], b))
+    nn = _node_counts(n_nodes, b, v, o)
     marg = p.astype(dt)
     logz = np.zeros(b, dt)
     scores = np.full((b, v, o), TREE_FORBIDDEN, np.int32)

@@ -22,9 +22,9 @@ import torch
 from .upload import Uploader
 
 from . import _lib
+from .evaluation import TREE_LOG2_FLOOR, tree_score_shift  # noqa: F401  (tree_score_shift: re-exported)
 
 SMALL_NUMBER = 1e-7   # utils.py
-TREE_LOG2_FLOOR = 150  # tree_scores: |log2| of the smallest positive float32 is 149
 
 
 class EmbedSegment(ctypes.Structure):          # include/ggnn.h: ggnn_embed_segment
@@ -261,8 +261,7 @@ class OutputHeads:
         if p_l.shape[:2] != (b, v):
             raise ValueError("probs: head %s and label %s shapes disagree" % (tuple(p_h.shape), tuple(p_l.shape)))
         dev = p_h.device
-        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
-            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
+        _check_n_nodes(n_nodes, b, dev)
         y_h = y_l = gold = None
         if labels is not None:
             y_h, y_l = (_decode_input(t, "labels") for t in labels)
@@ -277,6 +276,47 @@ class OutputHeads:
                    "ggnn_heads_decode")
         return pred, gold, counts
 
+    def _workspace(self, attr, need, dev, workspace=None):
+        """A pass's workspace of ``need`` bytes: the binding's own buffer
+        ``attr``, grown on demand (None when the pass asks for none), or the
+        caller's once it is checked."""
+        if workspace is None:
+            own = getattr(self, attr)
+            if need and (own is None or own.numel() < need or own.device != dev):
+                own = torch.empty(need, dtype=torch.uint8, device=dev)
+                setattr(self, attr, own)
+            return own if need else None
+        if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+            raise ValueError("workspace must be a contiguous uint8 tensor on %s" % dev)
+        if workspace.numel() < need:
+            raise ValueError("workspace of %d bytes, %d needed" % (workspace.numel(), need))
+        return workspace
+
+    def _tree_pass(self, name, attr, scores, n_nodes, pred, gold, counts, single_root, workspace=None):
+        """tree_decode / projective_decode: ggnn_<name> with its workspace."""
+        _check_tensor(scores, "scores", torch.int32)
+        b, v, o = scores.shape
+        dev = scores.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("%s needs v <= o and v <= %d (got v %d, o %d)" % (name, _lib.TREE_MAXV, v, o))
+        _check_n_nodes(n_nodes, b, dev)
+        if (gold is None) != (counts is None):
+            raise ValueError("gold and counts are given together")
+        _check_int32(pred, "pred", (b, v, 2), dev)
+        if gold is not None:
+            _check_int32(gold, "gold", (b, v, 2), dev)
+            _check_int32(counts, "counts", (b, _lib.DECODE_COUNTS), dev)
+        need = int(getattr(self._lib, "ggnn_%s_workspace_bytes" % name)(b, v))
+        workspace = self._workspace(attr, need, dev, workspace)
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(getattr(self._lib, "ggnn_" + name)(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes),
+                                                      int(bool(single_root)), _ptr(pred), _ptr(gold), _ptr(counts),
+                                                      _ptr(status), _ptr(workspace),
+                                                      0 if workspace is None else workspace.numel(), _stream()),
+                   "ggnn_" + name)
+        return status
+
     def tree_decode(self, scores, n_nodes, pred, gold=None, counts=None, single_root=True):
         """The tree post-pass on ``decode``'s pred, on the same stream
         (ggnn_tree_decode).  scores: int32 [b, v, o] (``tree_scores``);
@@ -286,17 +326,7 @@ class OutputHeads:
         status int32 [b]: 0 = pred's heads already were a tree, 1 = replaced
         by the maximum spanning tree of the scores, 2 = no tree exists (the
         graph is left as it was)."""
-        b, v, o, dev = _tree_args("tree_decode", scores, n_nodes, pred, gold, counts)
-        need = int(self._lib.ggnn_tree_decode_workspace_bytes(b, v))
-        if need and (self._tree_ws is None or self._tree_ws.numel() < need or self._tree_ws.device != dev):
-            self._tree_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        status = torch.empty(b, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(self._lib.ggnn_tree_decode(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes), int(bool(single_root)),
-                                              _ptr(pred), _ptr(gold), _ptr(counts), _ptr(status),
-                                              _ptr(self._tree_ws) if need else None, need, _stream()),
-                   "ggnn_tree_decode")
-        return status
+        return self._tree_pass("tree_decode", "_tree_ws", scores, n_nodes, pred, gold, counts, single_root)
 
     def projective_decode(self, scores, n_nodes, pred, gold=None, counts=None, single_root=True, workspace=None):
         """The projective post-pass on ``decode``'s pred, on the same stream
@@ -306,24 +336,8 @@ class OutputHeads:
         projective tree exists or the scores are out of range (the graph is
         left as it was).  workspace: a uint8 tensor to use instead of the
         binding's own (grown on demand; needed for v > PROJ_LDS_MAXN only)."""
-        b, v, o, dev = _tree_args("projective_decode", scores, n_nodes, pred, gold, counts)
-        need = int(self._lib.ggnn_projective_decode_workspace_bytes(b, v))
-        if workspace is None:
-            if need and (self._proj_ws is None or self._proj_ws.numel() < need or self._proj_ws.device != dev):
-                self._proj_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            workspace = self._proj_ws if need else None
-        elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
-            raise ValueError("workspace must be a contiguous uint8 tensor on %s" % dev)
-        elif workspace.numel() < need:
-            raise ValueError("workspace of %d bytes, %d needed" % (workspace.numel(), need))
-        status = torch.empty(b, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(self._lib.ggnn_projective_decode(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes),
-                                                    int(bool(single_root)), _ptr(pred), _ptr(gold), _ptr(counts),
-                                                    _ptr(status), _ptr(workspace),
-                                                    0 if workspace is None else workspace.numel(), _stream()),
-                   "ggnn_projective_decode")
-        return status
+        return self._tree_pass("projective_decode", "_proj_ws", scores, n_nodes, pred, gold, counts, single_root,
+                               workspace)
 
     def projective_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True, workspace=None):
         """The posterior marginal of every arc under the distribution over
@@ -337,25 +351,14 @@ class OutputHeads:
         instead of the binding's own (grown on demand; needed for v >
         MARG_LDS_MAXN only)."""
         p = probs_head
-        if p.dim() != 3 or p.dtype != torch.float32 or p.device.type != "cuda":
-            raise ValueError("probs_head must be a float32 [b, v, o] tensor on the GPU")
-        if not p.is_contiguous():
-            raise ValueError("probs_head must be contiguous")
+        _check_tensor(p, "probs_head", torch.float32)
         b, v, o = p.shape
         dev = p.device
         if v > o or v > _lib.TREE_MAXV:
             raise ValueError("projective_marginals needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
-        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
-            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
+        _check_n_nodes(n_nodes, b, dev)
         need = int(self._lib.ggnn_projective_marginals_workspace_bytes(b, v))
-        if workspace is None:
-            if need and (self._marg_ws is None or self._marg_ws.numel() < need or self._marg_ws.device != dev):
-                self._marg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            workspace = self._marg_ws if need else None
-        elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
-            raise ValueError("workspace must be a contiguous uint8 tensor on %s" % dev)
-        elif workspace.numel() < need:
-            raise ValueError("workspace of %d bytes, %d needed" % (workspace.numel(), need))
+        workspace = self._workspace("_marg_ws", need, dev, workspace)
         marg = torch.empty_like(p)
         logz = torch.empty(b, dtype=torch.float32, device=dev)
         scores = torch.empty(b, v, o, dtype=torch.int32, device=dev) if with_scores else None
@@ -378,10 +381,8 @@ class OutputHeads:
         dev = marg.device
         if v > o:
             raise ValueError("arc_confidence needs v <= o (got v %d, o %d)" % (v, o))
-        if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
-            raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
-        if pred.dtype != torch.int32 or pred.device != dev or tuple(pred.shape) != (b, v, 2) or not pred.is_contiguous():
-            raise ValueError("pred must be a contiguous int32 %s tensor on %s" % ([b, v, 2], dev))
+        _check_n_nodes(n_nodes, b, dev)
+        _check_int32(pred, "pred", (b, v, 2), dev)
         conf = torch.empty(b, v, dtype=torch.float32, device=dev)
         d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
         _lib.check(self._lib.ggnn_arc_confidence(ctypes.byref(d), _ptr(marg), o, _ptr(n_nodes), _ptr(pred),
@@ -389,36 +390,23 @@ class OutputHeads:
         return conf
 
 
-def _tree_args(name, scores, n_nodes, pred, gold, counts):
-    """The argument checks tree_decode and projective_decode share; returns
-    (b, v, o, device)."""
-    if scores.dim() != 3 or scores.dtype != torch.int32 or scores.device.type != "cuda":
-        raise ValueError("scores must be an int32 [b, v, o] tensor on the GPU")
-    if not scores.is_contiguous():
-        raise ValueError("scores must be contiguous")
-    b, v, o = scores.shape
-    dev = scores.device
-    if v > o or v > _lib.TREE_MAXV:
-        raise ValueError("%s needs v <= o and v <= %d (got v %d, o %d)" % (name, _lib.TREE_MAXV, v, o))
+def _check_n_nodes(n_nodes, b, dev):
     if n_nodes.dtype != torch.int32 or n_nodes.device != dev or n_nodes.numel() != b or not n_nodes.is_contiguous():
         raise ValueError("n_nodes must be a contiguous int32 tensor of %d elements on %s" % (b, dev))
-    if (gold is None) != (counts is None):
-        raise ValueError("gold and counts are given together")
-    for t, what, shape in ((pred, "pred", (b, v, 2)), (gold, "gold", (b, v, 2)),
-                           (counts, "counts", (b, _lib.DECODE_COUNTS))):
-        if t is not None and (t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape
-                              or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous int32 %s tensor on %s" % (what, list(shape), dev))
-    return b, v, o, dev
 
 
-def tree_score_shift(v):
-    """k of tree_scores: the largest k <= 16 with 150 * 2^k * v * (v + 1) <=
-    2^30 (evaluation.tree_score_shift; ggnn_tree_decode's exactness contract)."""
-    k = 16
-    while k > 0 and TREE_LOG2_FLOOR * int(v) * (int(v) + 1) * 2 ** k > 2 ** 30:
-        k -= 1
-    return k
+def _check_tensor(t, name, dtype):
+    """t: an int32 / float32 [b, v, o] tensor on the GPU, contiguous."""
+    kind = "an int32" if dtype == torch.int32 else "a float32"
+    if t.dim() != 3 or t.dtype != dtype or t.device.type != "cuda":
+        raise ValueError("%s must be %s [b, v, o] tensor on the GPU" % (name, kind))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+
+
+def _check_int32(t, name, shape, dev):
+    if t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous int32 %s tensor on %s" % (name, list(shape), dev))
 
 
 def tree_scores(probs_head, n_nodes, v):

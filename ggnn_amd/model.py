@@ -26,17 +26,9 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
   chem_tensorflow.py:483-506) -- all on the HIP library (``heads.py``).
 
 * not in the reference: ``predict_batch`` / ``parse`` (the predicted tree of a
-  batch / of raw sentences) and ``evaluate_batch(on_device=True)`` /
-  ``score_epoch`` (the scores from per-graph counts), decoded on the device by
-  ``ggnn_heads_decode`` (``csrc/k_decode.h``); with ``tree=True`` the heads
-  of a graph that is not a dependency tree are replaced by the maximum
-  spanning tree of the head scores (``ggnn_tree_decode``, ``csrc/k_tree.h``),
-  with ``tree="projective"`` the heads of a graph that is not a projective
-  tree by the best projective tree (``ggnn_projective_decode``,
-  ``csrc/k_proj.h``), with ``tree="projective-mbr"`` the minimum Bayes risk
-  projective tree of the arc marginals (``ggnn_projective_marginals``,
-  ``csrc/k_marg.h``); ``confidence=True`` adds the marginal of every returned
-  head
+  batch / of raw sentences), ``score_epoch`` and ``evaluate_batch(on_device=
+  True)`` (the scores from per-graph counts): ``decoding.DecodingMixin``, the
+  decode and the tree passes after it on the device (``tree=``, ``confidence=``)
 
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
@@ -65,30 +57,17 @@ from . import checkpoint as _ckpt
 from . import dist as _dist
 from . import evaluation as _eval
 from .batching import BtbBatching, ThreadedIterator
+from .decoding import DecodingMixin, _as_np, _tree_mode
 from .dist import FlatTrainBuffer
 from .engine import PropagationEngine
 from .graphs import CapturedStep, PinnedRing, StepLayout, edge_arrays
-from .heads import (SMALL_NUMBER, EmbedFunction, EmbeddingFrontEnd, HeadsFunction, OutputHeads, tree_scores,
-                    word_inputs_tensor)
+from .heads import SMALL_NUMBER, EmbedFunction, EmbeddingFrontEnd, HeadsFunction, OutputHeads, word_inputs_tensor
 from .optim import ClipAdam
 from .upload import PinnedFetch, Uploader
 
 GRU_KEYS = ("gates_kernel", "gates_bias", "candidate_kernel", "candidate_bias")
 # the path's weights in the order the engine's dicts and _Propagate take them
 PATH_KEYS = ("edge_weights", "edge_biases") + GRU_KEYS
-KEEP_KEYS = ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weight_dropout_keep_prob",
-             "emb_dropout_keep_prob")
-
-
-def _tree_mode(tree):
-    """The ``tree`` keyword of the decoding entries: False, True,
-    "projective" or "projective-mbr" (returned as given); anything else is a
-    ValueError."""
-    if isinstance(tree, (bool, np.bool_)):
-        return bool(tree)
-    if isinstance(tree, str) and tree in ("projective", "projective-mbr"):
-        return tree
-    raise ValueError('tree must be False, True, "projective" or "projective-mbr", got %r' % (tree,))
 
 
 def mlp_init(shape, rng):
@@ -150,7 +129,7 @@ class _Propagate(torch.autograd.Function):
         return (g["h0"], None, None, None, None, None) + tuple(g[k] for k in PATH_KEYS)
 
 
-class DenseGGNNChemModel(BtbBatching):
+class DenseGGNNChemModel(DecodingMixin, BtbBatching):
     """Hot-path subset of the reference's DenseGGNNChemModel (btb task)."""
 
     def __init__(self, args=None, params=None, num_edge_types=None, output_size_edges=12, pos_size=46,
@@ -908,10 +887,7 @@ class DenseGGNNChemModel(BtbBatching):
 
             if r["counts"] is None:          # masks not of get_mask's closed form: the host scorer
                 return self._score_batch()[:3]
-            counts = r["counts"]
-            if isinstance(counts, torch.Tensor):
-                counts = counts.cpu().numpy()
-            return _eval.scores_from_counts(counts, fallback)
+            return _eval.scores_from_counts(_as_np(r["counts"]), fallback)
         if feed_dict is not None:
             self.feed(feed_dict)
         # the staged placeholders as fed, only the output layer's dropout off
@@ -946,316 +922,6 @@ class DenseGGNNChemModel(BtbBatching):
         labels_e = np.asarray(ph["target_values_edges"], np.float32).reshape(b, v * oe)
         las, uas, uas_e = _eval.batch_las_uas(labels, probs, v, mask, labels_e, probs_e, mask_e, o, oe)
         return las, uas, uas_e, labels, probs, mask, labels_e, probs_e, mask_e
-
-    # ------------------------------------------- decoding (ggnn_heads_decode)
-    def _feed_n_nodes(self, ph):
-        """The graphs' node counts of a feed (node_mask_edges row sums /
-        output_size_edges) as int32 [b], or None when the feed's masks are not
-        of get_mask's closed form (the decode kernel rebuilds them from the
-        counts alone)."""
-        b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
-        o, oe = self.params["output_size"], self.output_size_edges
-        if v > o or ph.get("node_mask") is None or ph.get("node_mask_edges") is None:
-            return None
-        m = np.asarray(ph["node_mask"]).reshape(b, v, o)
-        m_e = np.asarray(ph["node_mask_edges"]).reshape(b, v, oe)
-        n = np.rint(m_e.sum(axis=(1, 2)) / oe).astype(np.int32)
-        ref, ref_e = _eval.closed_form_masks(n, v, o, oe)
-        if not (np.array_equal(m, ref) and np.array_equal(m_e, ref_e)):
-            return None
-        return n
-
-    def _eval_forward(self, feed):
-        """The dropout-free forward of a feed (a copy of it with the four keep
-        probabilities at 1.0 is staged): through its shape's captured step
-        when _graph_ok, else build_loss on the eager path.  Returns the loss."""
-        feed = dict(feed)
-        feed.update((k, 1.0) for k in KEEP_KEYS)
-        with torch.no_grad():
-            loss = self._graph_step(feed, False) if self._graph_ok(feed) else None
-            if loss is None:
-                self.graph_stats["eager"] += 1
-                self.feed(feed)
-                loss = self.build_loss()
-        return loss
-
-    def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False):
-        """_eval_forward of a feed (default: the staged one) followed by the
-        decode launch on the same stream.  Returns a dict: loss (scalar
-        tensor), ph (the staged placeholders), b, v, n_nodes (host int32 [b],
-        None: masks not in closed form) and pred / gold / counts -- int32
-        device tensors, numpy arrays on a CPU device (decode_arrays), None
-        without n_nodes.  tree: the tree post-pass follows the decode eagerly
-        on the same stream (never inside a captured step) and 'tree_status'
-        [b] joins the dict; a graph with regular == 0 is not passed to it
-        (node count 0) and gets status 2.  tree="projective": the projective
-        pass (ggnn_projective_decode, the host form on a CPU device) takes the
-        MST pass's place, on the same scores and with the same status rules.
-        tree="projective-mbr": after the decode the projective arc marginals of
-        the head probabilities (ggnn_projective_marginals on n * regular), the
-        decode again with the marginals in the head probabilities' place, and
-        the projective pass on the marginals' integer scores: the tree with
-        the most expected-correct heads.  'tree_status' is then 2 for a graph
-        that is not regular or has no marginals (it keeps its plain arg-max),
-        else the projective pass's own (0: the arg-max of the marginals was a
-        projective tree, 1: replaced by the MBR tree).  confidence (not with
-        tree=True): 'head_confidence' [b, v] float32, the marginal of every
-        returned head (ggnn_arc_confidence; for a graph without marginals the
-        head probability itself), and 'log_partition' [b] join the dict; the
-        marginals launch and the gather follow the other launches."""
-        mode = _tree_mode(tree)
-        projective, mbr = mode == "projective", mode == "projective-mbr"
-        if confidence and mode is True:
-            raise ValueError("confidence: a tree of tree=True may cross, it has no probability under the "
-                             "distribution over projective trees; use tree=False, \"projective\" or "
-                             "\"projective-mbr\"")
-        loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
-        ph = dict(self.placeholders)
-        b, v = int(ph["num_graphs"]), int(ph["num_vertices"])
-        o, oe = self.params["output_size"], self.output_size_edges
-        r = {"loss": loss.detach(), "ph": ph, "b": b, "v": v, "pred": None, "gold": None, "counts": None,
-             "tree_status": None, "head_confidence": None, "log_partition": None}
-        n = r["n_nodes"] = self._feed_n_nodes(ph)
-        if n is None:
-            return r
-        probs = self.ops["computed_values"].detach().reshape(b, v, o)
-        probs_e = self.ops["computed_values_edges"].detach().reshape(b, v, oe)
-        if probs.device.type != "cuda":
-            y = y_e = None
-            if with_gold:
-                y = np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o)
-                y_e = np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)
-            r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(probs.numpy(), probs_e.numpy(), n, y, y_e)
-            regular = r["counts"][:, 4] == 1
-            if mbr or confidence:
-                marg, logz, m_scores, m_status, _ = _eval.projective_marginals_arrays(
-                    probs.numpy(), np.where(regular, n, 0), single_root)
-                marg = marg.astype(np.float32)
-            if mbr:
-                r["pred"], r["gold"], r["counts"] = _eval.decode_arrays(marg, probs_e.numpy(), n, y, y_e)
-                pred, counts, status = _eval.projective_decode_arrays(
-                    m_scores, np.where(regular, n, 0), r["pred"], single_root, r["gold"],
-                    r["counts"] if with_gold else None)
-                r["pred"] = pred
-                r["tree_status"] = np.where(regular & (m_status == 1), status, 2).astype(np.int32)
-                if with_gold:
-                    r["counts"] = counts
-            elif tree:
-                host_pass = _eval.projective_decode_arrays if projective else _eval.tree_decode_arrays
-                pred, counts, status = host_pass(
-                    _eval.tree_scores(probs.numpy(), n, v), np.where(regular, n, 0), r["pred"], single_root,
-                    r["gold"], r["counts"] if with_gold else None)
-                r["pred"], r["tree_status"] = pred, np.where(regular, status, 2).astype(np.int32)
-                if with_gold:
-                    r["counts"] = counts
-            if confidence:
-                r["head_confidence"] = _eval.arc_confidence_arrays(marg, n, r["pred"])
-                r["log_partition"] = logz.astype(np.float32)
-            return r
-        n_dev = self._up_nodes(n, self.device)
-        heads = self._decode_heads()
-        labels = self._last_labels if with_gold else None
-        r["pred"], r["gold"], r["counts"] = heads.decode([probs, probs_e], n_dev, labels)
-        if mbr:
-            regular = r["counts"][:, 4] == 1
-            n_reg = (n_dev * regular).to(torch.int32)
-            marg, logz, m_scores, m_status = heads.projective_marginals(probs.contiguous(), n_reg, single_root)
-            r["pred"], r["gold"], r["counts"] = heads.decode([marg, probs_e], n_dev, labels)
-            status = heads.projective_decode(m_scores, n_reg, r["pred"], r["gold"],
-                                             r["counts"] if with_gold else None, single_root)
-            r["tree_status"] = torch.where(regular & (m_status == 1), status, torch.full_like(status, 2))
-        elif tree:
-            regular = r["counts"][:, 4] == 1
-            status = (heads.projective_decode if projective else heads.tree_decode)(
-                tree_scores(probs, n_dev, v), (n_dev * regular).to(torch.int32), r["pred"], r["gold"],
-                r["counts"] if with_gold else None, single_root)
-            r["tree_status"] = torch.where(regular, status, torch.full_like(status, 2))
-        if confidence:
-            if not mbr:
-                n_reg = (n_dev * (r["counts"][:, 4] == 1)).to(torch.int32)
-                marg, logz, _, _ = heads.projective_marginals(probs.contiguous(), n_reg, single_root,
-                                                              with_scores=False)
-            r["head_confidence"] = heads.arc_confidence(marg, n_dev, r["pred"])
-            r["log_partition"] = logz
-        return r
-
-    def _host_pred(self, ph, b, v):
-        """pred [b, v, 2] of the staged batch from its fetched probabilities and
-        the feed's own masks (a feed whose masks the decode cannot rebuild)."""
-        o, oe = self.params["output_size"], self.output_size_edges
-        return _eval.pred_from_masks(self.ops["computed_values"].detach().cpu().numpy(),
-                                     self.ops["computed_values_edges"].detach().cpu().numpy(),
-                                     np.asarray(ph["node_mask"], np.float32).reshape(b, v, o),
-                                     np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
-
-    def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False):
-        """The predicted tree of every graph of a batch: {'heads': [b, v],
-        'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
-        arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
-        prediction: node 0, padding, an all-zero row), 'n_nodes': [b],
-        'sentences_id', 'tree_status'}.  Runs the dropout-free forward and
-        decodes on the device; 2 * b * v int32 come back instead of both
-        probability arrays.  tree: 'heads' of a graph whose arg-max heads are
-        not a dependency tree (single_root: with one ROOT child) hold the
-        maximum spanning tree of the head scores instead (ggnn_tree_decode on
-        tree_scores of the head probabilities) and 'tree_status' [b] int32
-        says 0 = was a tree, 1 = repaired, 2 = no tree exists / not attempted
-        (left as the arg-max); None without tree.  tree="projective": 'heads'
-        of a graph whose arg-max heads are not a PROJECTIVE dependency tree
-        (no two arcs cross, ROOT at the leftmost position) hold the best
-        projective tree of the same scores instead (ggnn_projective_decode,
-        Eisner's algorithm); the MST pass does not run, and 'tree_status' says
-        0 = was a projective tree, 1 = repaired, 2 = no projective tree exists
-        / not attempted.  tree="projective-mbr": 'heads' hold the minimum
-        Bayes risk projective tree, the one with the most expected-correct
-        heads under the distribution over projective trees that the head
-        probabilities define (ggnn_projective_marginals, then
-        ggnn_projective_decode on the marginals' scores); 'tree_status' says 0
-        = the arg-max of the marginals was a projective tree, 1 = replaced by
-        the MBR tree, 2 = no projective tree / not attempted (the plain
-        arg-max).  confidence (with tree False, "projective" or
-        "projective-mbr"; ValueError with tree=True): the dict gains
-        'head_confidence' [b, v] float32, the projective marginal of every
-        returned head (0 where there is no prediction), and 'log_partition'
-        [b].  tree must be False, True, "projective" or "projective-mbr"."""
-        tree = _tree_mode(tree)
-        if confidence and tree is True:
-            raise ValueError("predict_batch: confidence needs tree=False, \"projective\" or \"projective-mbr\" "
-                             "(a crossing tree has no probability under the projective distribution)")
-        r = self._decode_forward(feed_dict, False, tree, single_root, confidence)
-        ph, b, v = r["ph"], r["b"], r["v"]
-        pred = r["pred"]
-        if pred is None:
-            pred = self._host_pred(ph, b, v)
-            n = np.rint(np.asarray(ph["node_mask_edges"]).reshape(b, -1).sum(axis=1)
-                        / self.output_size_edges).astype(np.int32)
-        else:
-            n = r["n_nodes"]
-            if isinstance(pred, torch.Tensor):
-                pred = pred.cpu().numpy()
-        status = r["tree_status"]
-        if tree and status is None:          # masks not in closed form: the repair is not attempted
-            status = np.full(b, 2, np.int32)
-        elif isinstance(status, torch.Tensor):
-            status = status.cpu().numpy()
-        out = {"heads": np.ascontiguousarray(pred[:, :, 0]), "labels": np.ascontiguousarray(pred[:, :, 1]),
-               "n_nodes": n, "sentences_id": ph.get("sentences_id"), "tree_status": status}
-        if confidence:
-            conf, logz = r["head_confidence"], r["log_partition"]
-            if conf is None:                 # masks not in closed form: no marginals
-                conf, logz = np.zeros((b, v), np.float32), np.full(b, np.nan, np.float32)
-            as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
-            out["head_confidence"], out["log_partition"] = as_np(conf), as_np(logz)
-        return out
-
-    def parse(self, raw_data, tree=False, single_root=True, confidence=False):
-        """Parse raw btb sentences (the dicts process_raw_graphs accepts;
-        'targets' may be absent): one entry per input sentence, in input
-        order, in the JSON's own 'targets' form [[head, label], ...] for nodes
-        1..n-1 with the label one-based -- what adj_mat_to_target(...,
-        is_probability=True) + merge_head_and_edge_graph give for the sentence.
-        A sentence process_raw_graphs drops (empty graph) yields [].  tree: as
-        predict_batch(tree=True): every sentence for which a dependency tree
-        exists comes back as one.  tree="projective": every sentence for which
-        a projective dependency tree exists comes back as one (no crossing
-        arcs; predict_batch(tree="projective")).  tree="projective-mbr": the
-        minimum Bayes risk projective tree (predict_batch).  confidence:
-        returns (trees, confidences) with confidences[k] a list of floats
-        aligned with trees[k], the projective marginal of each returned head;
-        ValueError with tree=True."""
-        tree = _tree_mode(tree)
-        if confidence and tree is True:
-            raise ValueError("parse: confidence needs tree=False, \"projective\" or \"projective-mbr\"")
-        raw = []
-        for k, d in enumerate(raw_data):
-            c = dict(d)
-            c.setdefault("targets", [])
-            c["id"] = k                      # (in the copy: the batches carry the input position)
-            raw.append(c)
-        out = [[] for _ in raw]
-        conf = [[] for _ in raw]
-        data = self.process_raw_graphs(raw, False)
-        for feed in self.make_minibatch_iterator(data, False):
-            p = self.predict_batch(feed, tree, single_root, confidence)
-            for g, (k, heads, labels) in enumerate(zip(p["sentences_id"], p["heads"], p["labels"])):
-                rg_h = [[int(x), 1] for x in heads[1:] if x >= 0]
-                rg_e = [[0, int(x) + 1] for x in labels[1:] if x >= 0]
-                out[k] = _eval.merge_head_and_edge_graph(rg_h, rg_e)
-                if confidence:
-                    conf[k] = [float(c) for x, c in zip(heads[1:], p["head_confidence"][g, 1:]) if x >= 0]
-        return (out, conf) if confidence else out
-
-    def score_epoch(self, data, tree=False, single_root=True):
-        """The validation pass of run_epoch with the scoring on the device:
-        per batch only the loss and the decode's counts [b, 5] are fetched
-        (pred / gold too for a batch with an irregular graph, scored through
-        the reference's lists; both probability arrays only for a feed whose
-        masks are not in closed form).  One batch in flight and the sums over
-        the ranks as in run_epoch.  Returns (loss, las, uas, label_acc,
-        instances_per_sec, steps) -- run_epoch's values.  ``decode_stats``
-        holds the pass's graphs, host-fallback graphs and fetched bytes.  tree:
-        the scores are those of the tree-constrained heads (ggnn_tree_decode
-        after the decode, its status [b] fetched beside the counts);
-        ``decode_stats`` counts the repaired graphs and those without a tree
-        (a graph on the host fallback is scored from its arg-max lists).
-        tree="projective": the same with the projective pass
-        (ggnn_projective_decode) in the MST pass's place; the same keys count
-        the graphs it repaired and those without a projective tree.
-        tree="projective-mbr": the MBR chain of predict_batch; the same bytes
-        are fetched, 'repaired_graphs' counts the graphs whose marginals'
-        arg-max was replaced by the MBR tree."""
-        tree = _tree_mode(tree)
-        stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0, "repaired_graphs": 0,
-                                     "infeasible_graphs": 0}
-
-        def step(feed, all_reduce):
-            r = self._decode_forward(feed, True, tree, single_root)
-            r["event"] = None
-            if r["counts"] is None:          # the host scorer decides: fetch what it reads
-                r["scored"] = self._score_batch()[:3]
-                r["host"] = [r["loss"].cpu()]
-                stats["d2h_bytes"] += 4 + 4 * r["b"] * r["v"] * (self.params["output_size"] + self.output_size_edges)
-                stats["fallback_graphs"] += r["b"]
-            elif isinstance(r["counts"], np.ndarray):   # a CPU device: decode_arrays' counts
-                r["host"] = [r["loss"].reshape(1), torch.from_numpy(r["counts"])]
-                if tree:
-                    r["host"].append(torch.from_numpy(r["tree_status"]))
-            else:
-                dev = [r["loss"].reshape(1), r["counts"]]
-                if tree:
-                    dev.append(r["tree_status"])
-                r["host"], r["event"] = self._fetch_counts.fetch(dev)
-                stats["d2h_bytes"] += sum(t.numel() * t.element_size() for t in dev)
-            return r
-
-        def consume(r):
-            batch_loss = float(r["host"][0].sum())
-            if r["counts"] is None:
-                scores = r["scored"]
-                if tree:
-                    stats["infeasible_graphs"] += r["b"]
-            else:
-                if tree:
-                    status = r["host"][2].numpy()
-                    stats["repaired_graphs"] += int((status == 1).sum())
-                    stats["infeasible_graphs"] += int((status == 2).sum())
-                lists = {}
-
-                def fallback(i):
-                    if not lists:
-                        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
-                        lists["pred"], lists["gold"] = as_np(r["pred"]), as_np(r["gold"])
-                        if isinstance(r["pred"], torch.Tensor):
-                            stats["d2h_bytes"] += 2 * lists["pred"].nbytes
-                    stats["fallback_graphs"] += 1
-                    return _eval.graph_scores_from_lists(lists["pred"][i], lists["gold"][i])
-
-                scores = _eval.scores_from_counts(r["host"][1].numpy(), fallback)
-            stats["graphs"] += r["b"]
-            return (r["b"], batch_loss) + tuple(scores)
-
-        processed, loss, las, uas, uas_e, steps, _, elapsed = self._epoch(data, False, step, consume)
-        return loss / processed, las / processed, uas / processed, uas_e / processed, processed / elapsed, steps
 
     def _epoch(self, data, is_training, step, consume, extra=None, announce=None):
         """One pass over ``data``: what run_epoch and score_epoch share.  The

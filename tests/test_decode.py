@@ -303,3 +303,25 @@ def test_score_epoch_equals_run_epoch_on_a_cpu_device():
     # the shared epoch loop's progress line changes no value
     loud = m.run_epoch("valid", data, False, verbose=True)
     assert (loud[0], loud[4], loud[5], loud[6], loud[16]) == (ref[0], ref[4], ref[5], ref[6], ref[16])
+
+
+def test_host_decoder_and_output_heads_take_the_same_arguments():
+    """decode_chain calls its two backends alike: the five methods of the host
+    adapter and of the device binding agree on the names, order, kinds and
+    defaults of the parameters the chain passes."""
+    import inspect
+    from ggnn_amd.decoding import HostDecoder
+    from ggnn_amd.heads import OutputHeads
+    a_pass = ("scores", "n_nodes", "pred", "gold", "counts", "single_root")
+    used = {"decode": ("probs", "n_nodes", "labels"), "tree_decode": a_pass, "projective_decode": a_pass,
+            "projective_marginals": ("probs_head", "n_nodes", "single_root", "with_scores"),
+            "arc_confidence": ("marg", "n_nodes", "pred")}
+    for name, params in used.items():
+        dev = inspect.signature(getattr(OutputHeads, name)).parameters
+        host = inspect.signature(getattr(HostDecoder, name)).parameters
+        want = ["self"] + list(params)
+        assert list(dev)[:len(want)] == want and list(host)[:len(want)] == want, name
+        for p in params:
+            assert (dev[p].kind, dev[p].default) == (host[p].kind, host[p].default), (name, p)
+        for sig in (dev, host):                                           # (a workspace): never required
+            assert all(sig[p].default is not inspect.Parameter.empty for p in list(sig)[len(want):]), name

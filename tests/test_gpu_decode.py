@@ -5,6 +5,7 @@ score_epoch against the host scorer.  Exact integer and bit equality only."""
 import numpy as np
 import pytest
 
+from decode_cases import _synthetic_model, _synthetic_raw, _torch
 from ggnn_amd import evaluation as E
 
 pytestmark = pytest.mark.gpu
@@ -14,13 +15,6 @@ SHAPES = [(3, 4, 150, 12),      # the smallest bucket
           (2, 130, 150, 65),    # partial third / second lane chunk
           (2, 6, 1024, 46),     # the widest head
           (2, 38, 150, 46)]
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test collected on a machine without a HIP device")
-    return torch
 
 
 def _n_vectors(b, v):
@@ -145,20 +139,6 @@ def test_two_launches_give_identical_bytes():
 
 
 # ------------------------------------------------------------------ the model
-def _synthetic_model(graphs):
-    from ggnn_amd.model import DenseGGNNChemModel
-    return DenseGGNNChemModel(params={"hidden_size": 64, "num_timesteps": 2, "batch_size": 5,
-                                      "compact_adjacency": True, "hip_graphs": graphs},
-                              num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=0, embedding_sizes=dict(loc=16, pos=8, word=24, edge=16))
-
-
-def _synthetic_raw():
-    from ggnn_amd.batching import synthetic_treebank
-    return synthetic_treebank(23, num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=2)
-
-
 def _host_lists_of_staged_batch(m, feed):
     """[[head, label], ...] per graph from the probabilities the model holds
     for the batch it just ran, through the reference's functions."""
@@ -248,3 +228,34 @@ def test_score_epoch_equals_run_epoch_on_real_dev_sentences():
     assert st["graphs"] == 40 and st["fallback_graphs"] == 0, st
     # fetched: the loss and [b, 5] counts per batch
     assert st["d2h_bytes"] == sum(4 + 4 * 5 * cv.shape[0] for cv in ref[8])
+
+
+@pytest.mark.parametrize("graphs", [False, True], ids=["eager", "captured"])
+def test_decode_chain_on_the_device_equals_the_host_adapter(graphs):
+    """The one chain (decoding.decode_chain) with the device binding as its
+    backend, as _decode_forward runs it, against the same chain with the host
+    adapter on the probabilities fetched from the same forward: pred, gold,
+    counts and tree_status element for element, for every tree mode whose
+    kernels are bit-exact against their host forms."""
+    _torch()
+    from ggnn_amd.decoding import HostDecoder, decode_chain
+    m = _synthetic_model(graphs)
+    data = m.process_raw_graphs(_synthetic_raw(), False)
+    o, oe = m.params["output_size"], m.output_size_edges
+    repaired = {False: 0, True: 0, "projective": 0}
+    for feed in m.make_minibatch_iterator(data, False):
+        for tree in repaired:
+            r = m._decode_forward(dict(feed), True, tree)
+            b, v, ph = r["b"], r["v"], r["ph"]
+            fetch = lambda key, w: m.ops[key].detach().reshape(b, v, w).cpu().numpy()
+            labels = [np.asarray(ph[key], np.float32).reshape(b, v, w)
+                      for key, w in (("target_values_head", o), ("target_values_edges", oe))]
+            host = decode_chain(HostDecoder(), fetch("computed_values", o), fetch("computed_values_edges", oe),
+                                r["n_nodes"], labels, tree)
+            assert (r["tree_status"] is None) == (host["tree_status"] is None) == (tree is False)
+            for key in ("pred", "gold", "counts") + (("tree_status",) if tree else ()):
+                got = r[key].cpu().numpy()
+                assert got.dtype == host[key].dtype == np.int32 and np.array_equal(got, host[key]), (tree, key)
+            if tree:
+                repaired[tree] += int((host["tree_status"] == 1).sum())
+    assert repaired[True] > 0 and repaired["projective"] > 0, repaired        # the passes had work to do

@@ -7,6 +7,7 @@ host's, its total may not."""
 import numpy as np
 import pytest
 
+from decode_cases import _batch_bytes, _device_scores, _synthetic_model, _synthetic_raw, _torch
 from ggnn_amd import evaluation as E
 from ggnn_amd._lib import PROJ_LDS_MAXN as L
 from test_projective_decode import check_projective_predictions, crossing_tree, only_crossing_tree, out_of_range
@@ -23,13 +24,6 @@ SHAPES = [(4, 4, 150),                       # the smallest bucket
           (2, 198, 198),                     # the largest reference bucket
           (1, 256, 256)]                     # GGNN_TREE_MAXV
 BIG = 2 ** 30                                # rows and columns >= n: never read (would break the range rule)
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test collected on a machine without a HIP device")
-    return torch
 
 
 def _node_counts(v):
@@ -254,33 +248,6 @@ def test_binding_validates_its_arguments():
 
 
 # ------------------------------------------------------------------ the model
-def _synthetic_model(graphs):
-    from ggnn_amd.model import DenseGGNNChemModel
-    return DenseGGNNChemModel(params={"hidden_size": 64, "num_timesteps": 2, "batch_size": 5,
-                                      "compact_adjacency": True, "hip_graphs": graphs},
-                              num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=0, embedding_sizes=dict(loc=16, pos=8, word=24, edge=16))
-
-
-def _synthetic_raw():
-    from ggnn_amd.batching import synthetic_treebank
-    return synthetic_treebank(23, num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=2)
-
-
-def _device_scores(m, n_nodes, v):
-    """tree_scores of the probabilities the model holds for the batch it just ran."""
-    import torch
-    from ggnn_amd.heads import tree_scores
-    b, o = len(n_nodes), m.params["output_size"]
-    probs = m.ops["computed_values"].detach().reshape(b, v, o)
-    return tree_scores(probs, torch.from_numpy(np.asarray(n_nodes)).to(probs.device), v).cpu().numpy()
-
-
-def _batch_bytes(m, data, per_graph):
-    return sum(4 + 4 * per_graph * int(f["num_graphs"]) for f in m.make_minibatch_iterator(data, False))
-
-
 @pytest.mark.parametrize("graphs", [False, True], ids=["eager", "captured"])
 def test_model_projective_keyword(graphs):
     torch = _torch()

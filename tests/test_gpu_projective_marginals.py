@@ -18,6 +18,7 @@ n (log2 n + 4) 2^-24 = 6e-7)."""
 import numpy as np
 import pytest
 
+from decode_cases import _batch_bytes, _synthetic_model, _synthetic_raw, _torch
 from ggnn_amd import evaluation as E
 from ggnn_amd._lib import MARG_LDS_MAXN as M
 from test_projective_decode import only_crossing_tree
@@ -35,13 +36,6 @@ SHAPES = [(4, 4, 150),                       # the smallest bucket
           (1, 198, 198),                     # the largest reference bucket
           (1, 256, 256)]                     # GGNN_TREE_MAXV
 KINDS = ("flat", "sparse", "peaked", "tiny")
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test collected on a machine without a HIP device")
-    return torch
 
 
 def _node_counts(v):
@@ -257,24 +251,6 @@ def test_binding_validates_its_arguments():
 
 
 # ------------------------------------------------------------------ the model
-def _synthetic_model(graphs):
-    from ggnn_amd.model import DenseGGNNChemModel
-    return DenseGGNNChemModel(params={"hidden_size": 64, "num_timesteps": 2, "batch_size": 5,
-                                      "compact_adjacency": True, "hip_graphs": graphs},
-                              num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=0, embedding_sizes=dict(loc=16, pos=8, word=24, edge=16))
-
-
-def _synthetic_raw():
-    from ggnn_amd.batching import synthetic_treebank
-    return synthetic_treebank(23, num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=2)
-
-
-def _batch_bytes(m, data, per_graph):
-    return sum(4 + 4 * per_graph * int(f["num_graphs"]) for f in m.make_minibatch_iterator(data, False))
-
-
 @pytest.mark.parametrize("graphs", [False, True], ids=["eager", "captured"])
 def test_model_mbr_and_confidence(graphs):
     torch = _torch()

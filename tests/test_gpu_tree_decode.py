@@ -6,6 +6,7 @@ tree may differ from the host's, its total may not."""
 import numpy as np
 import pytest
 
+from decode_cases import _device_scores, _synthetic_model, _synthetic_raw, _torch
 from ggnn_amd import evaluation as E
 from test_tree_decode import (F, all_ties, argmax_pred, check_tree_predictions, closed_group, finish, forbidden_row,
                               full_cycle, nested_cycle, no_root_child, three_roots, two_cycle)
@@ -19,13 +20,6 @@ SHAPES = [(4, 4, 150),      # the smallest bucket
           (2, 198, 198)]    # the largest reference bucket
 CYCLES = [two_cycle, full_cycle, nested_cycle, no_root_child, three_roots, all_ties]
 RANDOM_LAUNCHES = 3
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test collected on a machine without a HIP device")
-    return torch
 
 
 def _n_vectors(b, v):
@@ -204,29 +198,6 @@ def test_binding_validates_its_arguments():
 
 
 # ------------------------------------------------------------------ the model
-def _synthetic_model(graphs):
-    from ggnn_amd.model import DenseGGNNChemModel
-    return DenseGGNNChemModel(params={"hidden_size": 64, "num_timesteps": 2, "batch_size": 5,
-                                      "compact_adjacency": True, "hip_graphs": graphs},
-                              num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=0, embedding_sizes=dict(loc=16, pos=8, word=24, edge=16))
-
-
-def _synthetic_raw():
-    from ggnn_amd.batching import synthetic_treebank
-    return synthetic_treebank(23, num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=2)
-
-
-def _device_scores(m, n_nodes, v):
-    """tree_scores of the probabilities the model holds for the batch it just ran."""
-    import torch
-    from ggnn_amd.heads import tree_scores
-    b, o = len(n_nodes), m.params["output_size"]
-    probs = m.ops["computed_values"].detach().reshape(b, v, o)
-    return tree_scores(probs, torch.from_numpy(np.asarray(n_nodes)).to(probs.device), v).cpu().numpy()
-
-
 @pytest.mark.parametrize("graphs", [False, True], ids=["eager", "captured"])
 def test_predict_batch_and_parse_return_trees(graphs):
     _torch()

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from decode_cases import _synthetic_raw
 from ggnn_amd import evaluation as E
-from ggnn_amd.batching import synthetic_treebank
 from ggnn_amd.model import DenseGGNNChemModel
 
 F = E.TREE_FORBIDDEN
@@ -315,11 +315,6 @@ def _synthetic_model():
         return m.ops["loss"]
     m.build_loss = build_loss
     return m
-
-
-def _synthetic_raw():
-    return synthetic_treebank(23, num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=2)
 
 
 def check_tree_predictions(m, feed, staged_scores):
