@@ -79,7 +79,8 @@ class PropagationEngine:
         pairs with an incoming edge instead of every row of every non-empty
         tile) for batches staged from edge lists: "auto" = whenever such a
         batch runs the general path anyway (hidden not 128 / 256, v > 128 or
-        force_generic) and qualifies (hidden % 4 == 0, edges <= b*v); True =
+        force_generic) and qualifies (hidden % 4 == 0, edges <= b*v, counted
+        without repeats when a host edge list has more rows than that); True =
         for every qualifying edge-list batch (also hidden 128 / 256: pair mode
         implies the general path); False = never."""
         self.h = int(hidden)
@@ -224,6 +225,15 @@ class PropagationEngine:
                     raise IndexError("edge label outside 1..%d" % E)
                 if min(src.min(), dst.min()) < 0 or max(src.max(), dst.max()) >= v:
                     raise IndexError("edge node index outside 0..%d" % (v - 1))
+            if n > b * v and self._use_pairs(b, v, 0):
+                # more rows than pair mode stages: a repeated edge sets the same
+                # cells again, so drop the repeats; the path a batch takes then
+                # follows from its adjacency, not from how the feed lists it
+                gid = np.repeat(np.arange(b, dtype=np.int32), sizes)
+                u = np.unique(np.column_stack([gid, e_np]), axis=0)      # sorted: still grouped by graph
+                e_np = np.ascontiguousarray(u[:, 1:])
+                offs_np[1:] = np.cumsum(np.bincount(u[:, 0], minlength=b))
+                n = int(offs_np[-1])
             edges = self._up_edges(e_np, self.device)
             offs = self._up_offs(offs_np, self.device)
         self._sparse = self._use_pairs(b, v, n)

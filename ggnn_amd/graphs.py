@@ -9,11 +9,22 @@ graph launch.  A shape's first batch runs the same body eagerly (one-off
 shapes never pay for a capture); its second batch is captured and replayed.
 
 What stays fixed across replays of one graph (its key: batch shape (b, v),
-the word_inputs width, the dropout keep probabilities, train / eval): every
-device pointer (the step owns its engine -- adjacency, workspaces -- and its
-heads workspace; the variables, their Adam slots and the flat gradient buffer
-belong to the model), every launch shape and every host scalar the library
-bakes into a launch.  What changes per batch lives in one device buffer
+the word_inputs width, the dropout keep probabilities, train / eval, the task,
+whether Adam is in the graph and then grad_scale, the word table's layout, and
+the host scalars below): every device pointer (the step owns its engine --
+adjacency, workspaces -- and its heads workspace; the variables, their Adam
+slots and the flat gradient buffer belong to the model), every launch shape
+and every host scalar the library bakes into a launch.  Of those scalars the
+ones a caller may change on a live model are in the key, so a change captures
+a fresh step and never replays a stale one: params['num_timesteps'] and, with
+Adam in the graph, optimizer.lr / b1 / b2 / eps / clip (ggnn_adam_step_dev
+takes them by value).  The rest are fixed for the model's life, because the
+variables' shapes or the model's own buffers follow from them: hidden_size,
+output_size, output_size_edges, num_edge_types, use_edge_bias and the
+precision (the shapes of the weights and of each step's engine), the
+embedding sizes and word_inputs columns of the front-end (the tables), and
+SMALL_NUMBER.  make_optimizer replaces the Adam slots, so it drops every
+captured step.  What changes per batch lives in one device buffer
 (``StepInputs``) that the graph reads: word_inputs, the edge list and graph
 offsets (capacity b*v rows; the kernels read only rows [off[0], off[b])), both
 heads' labels, and the step scalars -- the three dropout seeds

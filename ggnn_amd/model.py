@@ -548,7 +548,14 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         simply add: one all-reduce of the flat buffer, and clip + Adam on the
         sums with grad_scale 1.  With dropout off this equals one process
         stepping the concatenated batch.  A feed with num_graphs == 0 (a rank
-        without a batch in the last global step) contributes zeros."""
+        without a batch in the last global step) contributes zeros.
+
+        Aliasing: on a captured step (_graph_step) without an all-reduce the
+        returned loss, ``ops["loss"]`` and ``ops["computed_values"]`` /
+        ``["computed_values_edges"]`` are the graph's static outputs, so the
+        next replay of the same shape overwrites them in place (stream
+        ordered).  Clone or fetch what must outlive the next step, as run_epoch
+        does (tests/test_gpu_graph_lifecycle.py pins this)."""
         if feed_dict is not None and int(feed_dict.get("num_graphs", 1)) == 0:
             return self._empty_train_step(all_reduce, grad_scale)
         if feed_dict is not None and self._graph_ok(feed_dict):
@@ -625,12 +632,18 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         # (grad_scale is baked into the captured Adam launch: part of the key)
         # (the word table's layout, dense or IndexedSlices, is captured too)
         sparse = bool(training) and self._sparse_call(self.train_buffer(), all_reduce)
-        key = (bool(training), adam, b, v, wi.shape[-1], keeps, task_id, float(grad_scale) if adam else 1.0, sparse)
         if training:
             fl = self.train_buffer()
             params = self.trainable_variables()
             if self.optimizer is None:
                 self.make_optimizer()
+        # (the host scalars a launch takes by value are part of the key too:
+        # the number of timesteps, and Adam's rates and clip norm when Adam is
+        # in the graph; a change captures a fresh step, the old one ages out)
+        opt = self.optimizer
+        baked = (int(self.params["num_timesteps"]),) + ((opt.lr, opt.b1, opt.b2, opt.eps, opt.clip) if adam else ())
+        key = (bool(training), adam, b, v, wi.shape[-1], keeps, task_id, float(grad_scale) if adam else 1.0, sparse,
+               baked)
         cs = self._graphs.get(key)
         if cs is None:
             cs = self._graphs[key] = CapturedStep(StepLayout(b, v, wi.shape[-1], o, oe), self._new_engine(),
@@ -688,6 +701,11 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
             cs.graph.replay()
             out = cs.out
             self.graph_stats["replayed"] += 1
+            # (a replay runs none of the body's Python: this batch's draws, as
+            # _forward records them)
+            self.last_embed = dict(keep=keeps[0], seed=seeds[0])
+            self.last_dropout = dict(edge_keep=keeps[1], state_keep=keeps[2], seed=seeds[1])
+            self.last_heads = dict(keep=keeps[3], seed=seeds[2], target_num=target_num)
         cs.runs += 1
         if cs.runs == 1:
             self._evict_graphs(keep=key)

@@ -13,10 +13,12 @@ def _torch():
     return torch
 
 
-def _synthetic_model(graphs):
+def _synthetic_model(graphs, hidden=64, **params):
+    """hidden 64: the general path; 128: the specialised kernels and the
+    fused forward (the embedding concat is 16 + 16 + 8 + 24 wide)."""
     from ggnn_amd.model import DenseGGNNChemModel
-    return DenseGGNNChemModel(params={"hidden_size": 64, "num_timesteps": 2, "batch_size": 5,
-                                      "compact_adjacency": True, "hip_graphs": graphs},
+    return DenseGGNNChemModel(params={"hidden_size": hidden, "num_timesteps": 2, "batch_size": 5,
+                                      "compact_adjacency": True, "hip_graphs": graphs, **params},
                               num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
                               seed=0, embedding_sizes=dict(loc=16, pos=8, word=24, edge=16))
 

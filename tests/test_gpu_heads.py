@@ -127,11 +127,13 @@ def _dev_model(torch, keep_all, hidden=128, batch_size=6, emb=None, big_batch=Fa
     return m, feeds
 
 
-def _check_train_step(m, fd):
+def _check_train_step(m, fd, adam=True):
     """One whole btb training step of the drop-in model against the oracle
     composed the same way, including the IndexedSlices clip norm of the
     embeddings and every dropout mask (replayed from the seeds the model
-    drew)."""
+    drew).  A compact feed's edge lists are densified for the oracle.
+    adam=False: the loss, the gradients and the lookup norms only (the Adam
+    reference below is the first step's, from zero slots)."""
     params = m.trainable_variables()
     before = [p.detach().cpu().numpy().astype(np.float64) for p in params]
     loss = m.train_step(fd)
@@ -148,7 +150,11 @@ def _check_train_step(m, fd):
     h0 = O.embed_forward(segs, wi, h, e["keep"], e["seed"])
     w64 = {"edge_weights": P(W["edge_weights"]), "edge_biases": P(W["edge_biases"])}
     w64.update({k: P(t) for k, t in W["node_gru"].items()})
-    A = np.asarray(fd["adjacency_matrix"], np.float64)
+    if fd.get("adjacency_matrix") is None:
+        from ggnn_amd.batching import graph_to_adj_mat_bd
+        A = np.stack([graph_to_adj_mat_bd(g, fd["num_vertices"], m.num_edge_types) for g in fd["adjacency_edges"]])
+    else:
+        A = np.asarray(fd["adjacency_matrix"], np.float64)
     dr = m.last_dropout
     hT, caches = O.forward(A, h0, w64, m.params["num_timesteps"],
                            dropout=dict(edge_keep=dr["edge_keep"], state_keep=dr["state_keep"], seed=dr["seed"]))
@@ -177,6 +183,8 @@ def _check_train_step(m, fd):
         if sqn[i] is not None:
             got = m.lookup_sqnorm[id(params[i])]
             assert abs(float(got) - sqn[i]) <= 1e-4 * sqn[i], i
+        if not adam:
+            continue
         n = np.sqrt(sqn[i]) if sqn[i] is not None else np.sqrt(np.sum(g * g))
         gc = g * clip / max(n, clip)
         mm, vv = 0.1 * gc, 0.001 * gc * gc

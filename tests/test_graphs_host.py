@@ -33,6 +33,34 @@ def test_step_layout_fill_places_every_input():
     assert np.array_equal(host[L.ye:L.ye + ye.nbytes].view(np.float32).reshape(ye.shape), ye)
 
 
+def test_step_layout_fill_leaves_rows_past_the_offsets_in_place():
+    """fill writes only the batch's own edge rows: after a shorter edge list
+    (or none) the earlier batch's rows past offs[b] are still there, and offs
+    alone delimits what is live (the staging kernels read rows [0, offs[b]):
+    what the captured steps' replays rely on)."""
+    b, v, ncols, o, oe = 2, 5, 6, 150, 12
+    L = StepLayout(b, v, ncols, o, oe)
+    rng = np.random.default_rng(1)
+    wi = rng.integers(0, 100, (b, v, ncols)).astype(np.int32)
+    yh = rng.random((b, v, o)).astype(np.float32)
+    ye = rng.random((b, v, oe)).astype(np.float32)
+    long_e = rng.integers(1, 5, (L.edge_capacity, 3)).astype(np.int32)
+    host = np.zeros(L.nbytes, np.uint8)
+    rows = lambda: host[L.edges:L.edges + long_e.nbytes].view(np.int32).reshape(-1, 3)
+    offs = lambda: host[L.offs:L.offs + (b + 1) * 4].view(np.int32).tolist()
+    L.fill(host, [1, 2, 3], 1, 2.0, wi, long_e, np.array([0, 6, 10], np.int32), yh, ye)
+    assert np.array_equal(rows(), long_e) and offs() == [0, 6, 10]
+    short_e = rng.integers(5, 9, (3, 3)).astype(np.int32)
+    L.fill(host, [4, 5, 6], 2, 2.0, wi, short_e, np.array([0, 1, 3], np.int32), yh, ye)
+    assert np.array_equal(rows()[:3], short_e) and np.array_equal(rows()[3:], long_e[3:])
+    assert offs() == [0, 1, 3]
+    L.fill(host, [7, 8, 9], 3, 2.0, wi, np.zeros((0, 3), np.int32), np.zeros(3, np.int32), yh, ye)
+    assert np.array_equal(rows()[:3], short_e) and np.array_equal(rows()[3:], long_e[3:])
+    assert offs() == [0, 0, 0]
+    # nothing beside the edge rows is left over from an earlier batch
+    assert list(host[0:24].view(np.uint64)) == [7, 8, 9] and host[24:32].view(np.int64)[0] == 3
+
+
 def test_edge_arrays_concatenate_and_validate():
     graphs = [[[0, 1, 1], [1, 2, 2]], [], [[2, 3, 0]]]
     e, offs = edge_arrays(graphs, 4, 3)
