@@ -35,12 +35,14 @@ EXPORTED = (
     "ggnn_tree_decode_workspace_bytes", "ggnn_tree_decode",
     "ggnn_projective_decode_workspace_bytes", "ggnn_projective_decode",
     "ggnn_projective_marginals_workspace_bytes", "ggnn_projective_marginals", "ggnn_arc_confidence",
+    "ggnn_tree_marginals_workspace_bytes", "ggnn_tree_marginals",
 )
 DECODE_COUNTS = 5   # include/ggnn.h GGNN_DECODE_COUNTS: n_kept, las, uas, lab, regular
 TREE_MAXV = 256                # include/ggnn.h GGNN_TREE_MAXV
 TREE_FORBIDDEN = -2 ** 31      # include/ggnn.h GGNN_TREE_FORBIDDEN
 PROJ_LDS_MAXN = 128            # include/ggnn.h GGNN_PROJ_LDS_MAXN
 MARG_LDS_MAXN = 107            # include/ggnn.h GGNN_MARG_LDS_MAXN
+LAPL_LDS_MAXN = 199            # include/ggnn.h GGNN_LAPL_LDS_MAXN
 NUM_KERNEL_KINDS = 11
 
 
@@ -150,6 +152,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
         lib.ggnn_projective_marginals.restype = _I
         lib.ggnn_projective_marginals.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
                                                   ctypes.c_size_t, _P]
+        lib.ggnn_tree_marginals_workspace_bytes.restype = ctypes.c_size_t
+        lib.ggnn_tree_marginals_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+        lib.ggnn_tree_marginals.restype = _I
+        lib.ggnn_tree_marginals.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
+                                            ctypes.c_size_t, _P]
         lib.ggnn_arc_confidence.restype = _I
         lib.ggnn_arc_confidence.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, _P, _P]
         lib.ggnn_dbg_gemm.restype = _I

@@ -24,6 +24,7 @@
 #include "k_tree.h"
 #include "k_proj.h"
 #include "k_marg.h"
+#include "k_lapl.h"
 #include "k_gemm.h"
 #include "k_gemm_ring.h"
 #include "k_generic.h"
@@ -1856,6 +1857,34 @@ int ggnn_arc_confidence(const ggnn_dims* d, const float* marg, int32_t o, const 
   Prof p(K_HEADS, s);
   hipLaunchKernelGGL(k_arc_confidence, dim3(grid1d((long)d->b * d->v)), dim3(256), 0, s, marg, (int)o,
                      (const int*)n_nodes, (int)d->b, (int)d->v, (const int*)pred, conf);
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+
+// arc marginals over all dependency trees (k_lapl.h); booked under the heads
+// kind
+static_assert(GGNN_LAPL_LDS_MAXN == LAPL_LDS_MAXN, "tree marginals constants");
+static_assert(sizeof(float) * LAPL_MAT_FLOATS + sizeof(LaplShared) <= 160 * 1024 &&
+                  sizeof(float) * LAPL_LDS_MAXN * LAPL_LD(LAPL_LDS_MAXN) + sizeof(LaplShared) > 160 * 1024,
+              "GGNN_LAPL_LDS_MAXN is the largest n whose matrix fits the LDS of a CU");
+size_t ggnn_tree_marginals_workspace_bytes(int32_t b, int32_t v) {
+  if (b < 1 || v <= GGNN_LAPL_LDS_MAXN) return 0;
+  return (size_t)b * 4 * (size_t)(v - 1) * (size_t)LAPL_LD(v - 1);
+}
+int ggnn_tree_marginals(const ggnn_dims* d, const float* probs_head, int32_t o, const int32_t* n_nodes,
+                        int32_t single_root, float* marg, float* logz, int32_t* scores, int32_t* status,
+                        void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  const char* const name = "tree_marginals";
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, !probs_head || !n_nodes || !marg || !logz || !status))
+    return rc;
+  if (marg == probs_head) return fail(GGNN_EINVAL, "tree_marginals: marg must not alias probs_head");
+  const size_t need = ggnn_tree_marginals_workspace_bytes(d->b, d->v);
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_tree_marginals, dim3((unsigned)d->b), dim3(LAPL_THREADS), 0, s, probs_head, (int)o,
+                     (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (int*)scores, (int*)status,
+                     need ? (float*)workspace : nullptr, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
   LAUNCHCHK();
   return GGNN_OK;
 }

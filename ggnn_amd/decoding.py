@@ -1,9 +1,9 @@
 """Decoding: the chain decode -> marginals -> tree / projective pass ->
-confidences, written once against a backend with the device binding's five
+confidences, written once against a backend with the device binding's six
 methods (``decode``, ``tree_decode``, ``projective_decode``,
-``projective_marginals``, ``arc_confidence``): heads.OutputHeads on the GPU,
-``HostDecoder`` over evaluation.*_arrays for a model on a CPU device; and the
-model's decoding entries (``DecodingMixin``)."""
+``projective_marginals``, ``tree_marginals``, ``arc_confidence``):
+heads.OutputHeads on the GPU, ``HostDecoder`` over evaluation.*_arrays for a
+model on a CPU device; and the model's decoding entries (``DecodingMixin``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -14,25 +14,44 @@ from .heads import tree_scores
 
 KEEP_KEYS = ("out_layer_dropout_keep_prob", "graph_state_keep_prob", "edge_weight_dropout_keep_prob",
              "emb_dropout_keep_prob")
-_NO_CONFIDENCE = {      # confidence with tree=True, in each entry's words
+_NO_CONFIDENCE = {      # the projective confidence with tree=True / "mbr", in each entry's words
     "_decode_forward": "confidence: a tree of tree=True may cross, it has no probability under the distribution "
-                       "over projective trees; use tree=False, \"projective\" or \"projective-mbr\"",
+                       "over projective trees; use tree=False, \"projective\" or \"projective-mbr\", or "
+                       "confidence=\"nonprojective\"",
     "predict_batch": "predict_batch: confidence needs tree=False, \"projective\" or \"projective-mbr\" "
-                     "(a crossing tree has no probability under the projective distribution)",
-    "parse": "parse: confidence needs tree=False, \"projective\" or \"projective-mbr\""}
+                     "(a crossing tree has no probability under the projective distribution), or "
+                     "confidence=\"nonprojective\"",
+    "parse": "parse: confidence needs tree=False, \"projective\" or \"projective-mbr\", or "
+             "confidence=\"nonprojective\""}
+_MBR_FAMILY = {"projective-mbr": "projective", "mbr": "nonprojective"}     # the marginals an MBR mode is built on
+
+
+def _confidence_mode(confidence):
+    """The ``confidence`` keyword: False, "projective" (True means it) or
+    "nonprojective"; anything else is a ValueError."""
+    if isinstance(confidence, (bool, np.bool_)):
+        return "projective" if confidence else False
+    if isinstance(confidence, str) and confidence in ("projective", "nonprojective"):
+        return confidence
+    raise ValueError('confidence must be False, True, "projective" or "nonprojective", got %r' % (confidence,))
 
 
 def _tree_mode(tree, confidence=False, caller=None):
     """The ``tree`` keyword of the decoding entries: False, True,
-    "projective" or "projective-mbr" (returned as given); anything else is a
-    ValueError, and so is ``confidence`` with tree=True (``caller``'s text)."""
+    "projective", "projective-mbr" or "mbr" (returned as given); anything else
+    is a ValueError.  The distribution of ``confidence`` must contain the
+    returned tree: the projective one (True) with tree=True or "mbr" is a
+    ValueError too (``caller``'s text)."""
+    projective_conf = _confidence_mode(confidence) == "projective"
     if isinstance(tree, (bool, np.bool_)):
-        if tree and confidence:
+        if tree and projective_conf:
             raise ValueError(_NO_CONFIDENCE[caller])
         return bool(tree)
-    if isinstance(tree, str) and tree in ("projective", "projective-mbr"):
+    if isinstance(tree, str) and tree in ("projective", "projective-mbr", "mbr"):
+        if tree == "mbr" and projective_conf:
+            raise ValueError(_NO_CONFIDENCE[caller])
         return tree
-    raise ValueError('tree must be False, True, "projective" or "projective-mbr", got %r' % (tree,))
+    raise ValueError('tree must be False, True, "projective", "projective-mbr" or "mbr", got %r' % (tree,))
 
 
 def _as_np(t):
@@ -52,8 +71,8 @@ def _in_place(host_form):
 
 
 class HostDecoder:
-    """OutputHeads' five decoding methods over the host forms, numpy in and
-    out; the marginals as float32, without the host form's span_max."""
+    """OutputHeads' six decoding methods over the host forms, numpy in and
+    out; the marginals as float32, without the host forms' span_max / cond."""
     tree_decode = _in_place(_eval.tree_decode_arrays)
     projective_decode = _in_place(_eval.projective_decode_arrays)
 
@@ -62,6 +81,10 @@ class HostDecoder:
 
     def projective_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True):
         marg, logz, scores, status, _ = _eval.projective_marginals_arrays(probs_head, n_nodes, single_root)
+        return marg.astype(np.float32), logz.astype(np.float32), scores if with_scores else None, status
+
+    def tree_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True):
+        marg, logz, scores, status, _ = _eval.tree_marginals_arrays(probs_head, n_nodes, single_root)
         return marg.astype(np.float32), logz.astype(np.float32), scores if with_scores else None, status
 
     def arc_confidence(self, marg, n_nodes, pred):
@@ -79,30 +102,33 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     """The decode and what follows it, in launch order and in ``backend``'s
     array type (probs [b, v, o], probs_e [b, v, oe] float32, n_nodes int32
     [b], labels: the two heads' targets or None).  mode True / "projective":
-    the MST / projective pass on tree_scores of probs; "projective-mbr": the
-    marginals of probs, the decode again with them in probs' place, the
-    projective pass on their integer scores; confidence: the marginals (unless
-    MBR made them) and the gather of the returned heads' marginals come last.
-    The passes and the marginals see n * regular; tree_status is the pass's own
-    where a graph is regular (MBR: and has marginals), 2 elsewhere."""
-    on_device, mbr = isinstance(probs, torch.Tensor), mode == "projective-mbr"
+    the MST / projective pass on tree_scores of probs; "projective-mbr" /
+    "mbr": the projective / matrix-tree marginals of probs, the decode again
+    with them in probs' place, the projective / MST pass on their integer
+    scores; confidence ("projective", which True means, or "nonprojective"):
+    that distribution's marginals (unless MBR made them) and the gather of the
+    returned heads' marginals come last.  The passes and the marginals see n *
+    regular; tree_status is the pass's own where a graph is regular (MBR: and
+    has marginals), 2 elsewhere."""
+    on_device, family, confidence = isinstance(probs, torch.Tensor), _MBR_FAMILY.get(mode), _confidence_mode(confidence)
+    marginals = lambda kind: backend.projective_marginals if kind == "projective" else backend.tree_marginals
     pred, gold, counts = backend.decode([probs, probs_e], n_nodes, labels)
     regular = counts[:, 4] == 1
     n_reg = _select(regular, n_nodes, 0) if mode or confidence else None
-    if mbr:
-        marg, logz, scores, has_marg = backend.projective_marginals(probs, n_reg, single_root)
+    if family:
+        marg, logz, scores, has_marg = marginals(family)(probs, n_reg, single_root)
         pred, gold, counts = backend.decode([marg, probs_e], n_nodes, labels)
         regular = regular & (has_marg == 1)
     elif mode:
         scores = (tree_scores if on_device else _eval.tree_scores)(probs, n_nodes, probs.shape[1])
     out = {"pred": pred, "gold": gold, "counts": counts, "tree_status": None}
     if mode:
-        run = backend.tree_decode if mode is True else backend.projective_decode
+        run = backend.tree_decode if mode in (True, "mbr") else backend.projective_decode
         status = run(scores, n_reg, pred, gold, None if gold is None else counts, single_root)
         out["tree_status"] = _select(regular, status, 2)
     if confidence:
-        if not mbr:     # (nothing reads the integer scores)
-            marg, logz, _, _ = backend.projective_marginals(probs, n_reg, single_root, with_scores=False)
+        if family != confidence:     # (nothing reads the integer scores)
+            marg, logz, _, _ = marginals(confidence)(probs, n_reg, single_root, with_scores=False)
         out["head_confidence"], out["log_partition"] = backend.arc_confidence(marg, n_nodes, pred), logz
     return out
 
@@ -204,11 +230,19 @@ class DecodingMixin:
         ggnn_projective_decode on the marginals' scores); 'tree_status' says 0
         = the arg-max of the marginals was a projective tree, 1 = replaced by
         the MBR tree, 2 = no projective tree / not attempted (the plain
-        arg-max).  confidence (with tree False, "projective" or
-        "projective-mbr"; ValueError with tree=True): the dict gains
-        'head_confidence' [b, v] float32, the projective marginal of every
-        returned head (0 where there is no prediction), and 'log_partition'
-        [b].  tree must be False, True, "projective" or "projective-mbr"."""
+        arg-max).  tree="mbr": the same over ALL dependency trees, crossing
+        arcs included (ggnn_tree_marginals, the matrix-tree theorem, then
+        ggnn_tree_decode on the marginals' scores); 'tree_status' says 0 =
+        the arg-max of the marginals was a tree, 1 = replaced by the MBR
+        tree, 2 = no tree / not attempted.  confidence: the dict gains
+        'head_confidence' [b, v] float32, the marginal of every returned head
+        (0 where there is no prediction), and 'log_partition' [b], ln Z of
+        the distribution: True or "projective": over projective trees (with
+        tree False, "projective" or "projective-mbr"; ValueError with
+        tree=True or "mbr", whose trees that distribution need not contain);
+        "nonprojective": over all dependency trees, with every value of tree
+        (with tree="mbr" the marginals are computed once).  tree must be
+        False, True, "projective", "projective-mbr" or "mbr"."""
         tree = _tree_mode(tree, confidence, "predict_batch")
         r = self._decode_forward(feed_dict, False, tree, single_root, confidence)
         ph, b, v, pred = r["ph"], r["b"], r["v"], r["pred"]
@@ -241,10 +275,13 @@ class DecodingMixin:
         exists comes back as one.  tree="projective": every sentence for which
         a projective dependency tree exists comes back as one (no crossing
         arcs; predict_batch(tree="projective")).  tree="projective-mbr": the
-        minimum Bayes risk projective tree (predict_batch).  confidence:
+        minimum Bayes risk projective tree, tree="mbr": the minimum Bayes
+        risk tree over all dependency trees (predict_batch).  confidence:
         returns (trees, confidences) with confidences[k] a list of floats
-        aligned with trees[k], the projective marginal of each returned head;
-        ValueError with tree=True."""
+        aligned with trees[k], the marginal of each returned head: True or
+        "projective" under the distribution over projective trees (ValueError
+        with tree=True or "mbr"), "nonprojective" under the one over all
+        dependency trees (every value of tree)."""
         tree = _tree_mode(tree, confidence, "parse")
         # (copies: the batches carry the input position as 'id')
         raw = [{"targets": [], **d, "id": k} for k, d in enumerate(raw_data)]
@@ -278,7 +315,8 @@ class DecodingMixin:
         the graphs it repaired and those without a projective tree.
         tree="projective-mbr": the MBR chain of predict_batch; the same bytes
         are fetched, 'repaired_graphs' counts the graphs whose marginals'
-        arg-max was replaced by the MBR tree."""
+        arg-max was replaced by the MBR tree.  tree="mbr": the same with the
+        chain over all dependency trees (ggnn_tree_marginals, ggnn_tree_decode)."""
         tree = _tree_mode(tree)
         stats = self.decode_stats = {"graphs": 0, "fallback_graphs": 0, "d2h_bytes": 0, "repaired_graphs": 0,
                                      "infeasible_graphs": 0}

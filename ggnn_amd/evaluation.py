@@ -842,3 +842,124 @@ def arc_confidence_arrays(marg, n_nodes, pred):
     ok = (h >= 0) & (h < o) & (i >= 1) & (i < n[:, None])
     got = np.take_along_axis(mg, np.where(ok, h, 0)[:, :, None], axis=2)[:, :, 0]
     return np.where(ok, got, 0).astype(np.float32)
+
+
+# ------------------------------------------------ non-projective arc marginals
+# Host form of ``ggnn_tree_marginals`` (include/ggnn.h, csrc/k_lapl.h): the
+# distribution over ALL dependency trees by the matrix-tree theorem (Koo et al.
+# 2007; Smith & Smith 2007; McDonald & Satta 2007), np.linalg in place of the
+# kernel's Gauss-Jordan elimination.
+LAPL_LDS_MAXN = 199            # GGNN_LAPL_LDS_MAXN
+
+
+def _normalised_potentials(p, n, dt):
+    """One graph: (w [n, n] in dt, ok [n, n], ln_c float64).  w: the allowed
+    potentials (tree_scores' rule) with every word's row divided by its own sum
+    c[i], 0 elsewhere; a row is scaled by the power of two of its largest entry
+    before it is summed (exact, so a row of fp32 subnormals loses nothing);
+    ln_c = sum ln c[i].  A word without an allowed arc keeps a zero row."""
+    q = np.asarray(p)[:n, :n].astype(np.float32)
+    ok = np.isfinite(q) & (q > 0)
+    ok[0, :] = False
+    ok[np.arange(n), np.arange(n)] = False
+    x = np.where(ok, q, np.float32(0))
+    _, e = np.frexp(x.max(axis=1))
+    scaled = np.ldexp(x, -e[:, None]).astype(dt)
+    c = scaled.sum(axis=1, dtype=dt)
+    live = c > 0
+    w = scaled / np.where(live, c, 1).astype(dt)[:, None]
+    ln_c = float(np.sum(np.log(c[live].astype(np.float64)) + e[live] * np.log(2.0)))
+    return w.astype(dt), ok, ln_c
+
+
+def _has_tree(ok, n, single_root):
+    """Whether a dependency tree exists over the allowed arcs ok[i, j] ("word i
+    may take head j"), decided on the arcs alone: without single_root every
+    word is reachable from node 0 walking head -> dependent; with it some word
+    with an allowed ROOT arc reaches every other word among the words."""
+    reach = ok.T | np.eye(n, dtype=bool)                # reach[j, i]: i is j or a dependent of j
+    hops = 1
+    while hops < n:                                     # boolean squaring: paths of up to 2^t arcs
+        reach = (reach.astype(np.int32) @ reach.astype(np.int32)) > 0
+        hops *= 2
+    if not single_root:
+        return bool(reach[0, 1:].all())
+    return bool((ok[1:, 0] & reach[1:, 1:].all(axis=1)).any())
+
+
+def _laplacian(w, n, single_root):
+    """A [(n-1), (n-1)] over the words of the normalised potentials w:
+    A[h][d] = -w(d, h), A[d][d] = r(d) + sum_h w(d, h); single_root (Koo et
+    al.): A[d][d] = sum_h w(d, h) and the first word's row holds r(.)."""
+    W, r = w[1:, 1:], w[1:, 0]
+    A = -W.T.copy()
+    inner = W.sum(axis=1, dtype=w.dtype)
+    A[np.arange(n - 1), np.arange(n - 1)] = inner if single_root else inner + r
+    if single_root:
+        A[0, :] = r
+    return A
+
+
+def tree_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.float64):
+    """The host form of ``ggnn_tree_marginals`` (include/ggnn.h): probs_head
+    float32 [b, v, o], n_nodes [b].  The potentials are those of
+    projective_marginals_arrays; a dependency tree (single_root: one ROOT
+    child) weighs the product of its words' potentials and need not be
+    projective.  Returns (marg [b, v, o], logz [b], scores int32 [b, v, o],
+    status int32 [b], cond [b]) under projective_marginals_arrays' contract
+    (status 2: no tree exists, decided by reachability over the allowed arcs;
+    also a determinant that is not positive or a ln Z that is not finite).
+    cond[g]: the 1-norm condition number of the graph's normalised matrix in
+    float64 (1 for n < 3, inf for status 2): an elimination in fp32 is off by
+    about n * cond * 2^-24.  Matrix, inverse and determinant in ``dtype``."""
+    p = np.asarray(probs_head, np.float32)
+    if p.ndim != 3:
+        raise ValueError("probs_head must be [b, v, o]")
+    b, v, o = p.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("tree marginals need v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    dt = np.dtype(dtype)
+    single_root = bool(single_root)
+    nn = _node_counts(n_nodes, b, v, o)
+    marg = p.astype(dt)
+    logz = np.zeros(b, dt)
+    scores = np.full((b, v, o), TREE_FORBIDDEN, np.int32)
+    status = np.zeros(b, np.int32)
+    cond = np.ones(b, np.float64)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2:
+            continue
+        w, ok, ln_c = _normalised_potentials(p[g], n, dt)
+        status[g], logz[g], cond[g] = 2, -np.inf, np.inf
+        if not _has_tree(ok, n, single_root):
+            continue
+        A = _laplacian(w, n, single_root)
+        try:
+            sign, ln_det = np.linalg.slogdet(A)
+            B = np.linalg.inv(A)
+        except np.linalg.LinAlgError:
+            continue
+        lz = dt.type(float(ln_det) + ln_c)
+        if not (sign > 0 and np.isfinite(lz) and np.isfinite(B).all()):
+            continue
+        W, r, diag = w[1:, 1:], w[1:, 0], np.diag(B)
+        mg = np.zeros((n, n), dt)
+        if single_root:
+            first = np.arange(n - 1) == 0
+            mg[1:, 1:] = np.where(first[:, None], 0, W * diag[:, None]) - np.where(first[None, :], 0, W * B)
+            mg[1:, 0] = r * B[:, 0]
+        else:
+            mg[1:, 1:] = W * (diag[:, None] - B)
+            mg[1:, 0] = r * diag
+        status[g], logz[g] = 1, lz
+        if n >= 3:
+            cond[g] = float(np.linalg.cond(_laplacian(_normalised_potentials(p[g], n, np.dtype(np.float64))[0], n,
+                                                      single_root), 1))
+        else:
+            cond[g] = 1.0
+        marg[g] = 0
+        marg[g, :n, :n] = np.where(ok, np.clip(mg, 0, 1), 0)
+        scores[g, :n, :n] = np.where(ok, np.rint(marg[g, :n, :n].astype(np.float32) * np.float32(MARG_SCORE_SCALE)),
+                                     TREE_FORBIDDEN).astype(np.int32)
+    return marg, logz, scores, status, cond

@@ -175,6 +175,7 @@ class OutputHeads:
         self._tree_ws = None   # ggnn_tree_decode's workspace (the kernel asks for none today)
         self._proj_ws = None   # ggnn_projective_decode's workspace (graphs above PROJ_LDS_MAXN nodes)
         self._marg_ws = None   # ggnn_projective_marginals' workspace (graphs above MARG_LDS_MAXN nodes)
+        self._lapl_ws = None   # ggnn_tree_marginals' workspace (graphs above LAPL_LDS_MAXN nodes)
         self._saved = None
 
     def _table(self, heads, labels, probs, dws=None, dbs=None):
@@ -339,6 +340,29 @@ class OutputHeads:
         return self._tree_pass("projective_decode", "_proj_ws", scores, n_nodes, pred, gold, counts, single_root,
                                workspace)
 
+    def _marginals_pass(self, name, attr, p, n_nodes, single_root, with_scores, workspace):
+        """projective_marginals / tree_marginals: ggnn_<name> with its outputs
+        and its workspace."""
+        _check_tensor(p, "probs_head", torch.float32)
+        b, v, o = p.shape
+        dev = p.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("%s needs v <= o and v <= %d (got v %d, o %d)" % (name, _lib.TREE_MAXV, v, o))
+        _check_n_nodes(n_nodes, b, dev)
+        need = int(getattr(self._lib, "ggnn_%s_workspace_bytes" % name)(b, v))
+        workspace = self._workspace(attr, need, dev, workspace)
+        marg = torch.empty_like(p)
+        logz = torch.empty(b, dtype=torch.float32, device=dev)
+        scores = torch.empty(b, v, o, dtype=torch.int32, device=dev) if with_scores else None
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(getattr(self._lib, "ggnn_" + name)(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes),
+                                                      int(bool(single_root)), _ptr(marg), _ptr(logz), _ptr(scores),
+                                                      _ptr(status), _ptr(workspace),
+                                                      0 if workspace is None else workspace.numel(), _stream()),
+                   "ggnn_" + name)
+        return marg, logz, scores, status
+
     def projective_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True, workspace=None):
         """The posterior marginal of every arc under the distribution over
         projective trees that the head probabilities define, on the current
@@ -350,26 +374,20 @@ class OutputHeads:
         and scores are all forbidden).  workspace: a uint8 tensor to use
         instead of the binding's own (grown on demand; needed for v >
         MARG_LDS_MAXN only)."""
-        p = probs_head
-        _check_tensor(p, "probs_head", torch.float32)
-        b, v, o = p.shape
-        dev = p.device
-        if v > o or v > _lib.TREE_MAXV:
-            raise ValueError("projective_marginals needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
-        _check_n_nodes(n_nodes, b, dev)
-        need = int(self._lib.ggnn_projective_marginals_workspace_bytes(b, v))
-        workspace = self._workspace("_marg_ws", need, dev, workspace)
-        marg = torch.empty_like(p)
-        logz = torch.empty(b, dtype=torch.float32, device=dev)
-        scores = torch.empty(b, v, o, dtype=torch.int32, device=dev) if with_scores else None
-        status = torch.empty(b, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(self._lib.ggnn_projective_marginals(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes),
-                                                       int(bool(single_root)), _ptr(marg), _ptr(logz), _ptr(scores),
-                                                       _ptr(status), _ptr(workspace),
-                                                       0 if workspace is None else workspace.numel(), _stream()),
-                   "ggnn_projective_marginals")
-        return marg, logz, scores, status
+        return self._marginals_pass("projective_marginals", "_marg_ws", probs_head, n_nodes, single_root, with_scores,
+                                    workspace)
+
+    def tree_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True, workspace=None):
+        """The posterior marginal of every arc under the distribution over ALL
+        dependency trees (crossing arcs included) that the head probabilities
+        define, on the current stream (ggnn_tree_marginals: the matrix-tree
+        theorem).  Arguments, checks and the returned (marg, logz, scores or
+        None, status) are projective_marginals'; status 2 = no dependency
+        tree exists; ``tree_decode`` on the scores gives the minimum Bayes
+        risk tree.  workspace: a uint8 tensor to use instead of the binding's
+        own (grown on demand; needed for v > LAPL_LDS_MAXN only)."""
+        return self._marginals_pass("tree_marginals", "_lapl_ws", probs_head, n_nodes, single_root, with_scores,
+                                    workspace)
 
     def arc_confidence(self, marg, n_nodes, pred):
         """conf float32 [b, v]: marg[g, i, pred[g, i, 0]], 0 where there is no

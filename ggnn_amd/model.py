@@ -886,7 +886,8 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         as predict_batch(tree=True) returns them); tree="projective": by the
         best projective tree when they are not a projective tree
         (ggnn_projective_decode); tree="projective-mbr": by the minimum Bayes
-        risk projective tree (predict_batch).  Any other value of tree raises
+        risk projective tree, tree="mbr": by the minimum Bayes risk tree over
+        all dependency trees (predict_batch).  Any other value of tree raises
         ValueError."""
         if _tree_mode(tree) and not on_device:
             raise ValueError("evaluate_batch: tree=True needs on_device=True")

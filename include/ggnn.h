@@ -562,6 +562,58 @@ int ggnn_arc_confidence(const ggnn_dims* d,              /* b, v used */
                         float* conf,                     /* device [b][v] out */
                         ggnn_stream_t stream);
 
+/* Arc marginals over ALL dependency trees (the matrix-tree theorem): what
+ * ggnn_projective_marginals is to ggnn_projective_decode, this is to
+ * ggnn_tree_decode.  Potentials, allowed arcs and the clamping of n are
+ * ggnn_projective_marginals'; a dependency tree (single_root: exactly one ROOT
+ * child) weighs the product of its words' potentials and may have crossing
+ * arcs.  The outputs and their contract are ggnn_projective_marginals', word
+ * for word: logz[g], marg[g][i][j] (0 for an arc that is not allowed, row 0,
+ * rows and columns >= n; clamped to [0, 1]), scores[g][i][j] (when not NULL)
+ * rint(marg * 2^20) on allowed arcs and GGNN_TREE_FORBIDDEN elsewhere --
+ * ggnn_tree_decode, exact for every int32 score, gives their minimum Bayes
+ * risk tree --, status[g] = 1 written, 0 n < 2 (logz = 0), 2 no tree (logz =
+ * -inf); for status != 1 marg[g] is a copy of probs_head[g] and scores[g] is
+ * GGNN_TREE_FORBIDDEN everywhere.  marg must not alias probs_head.
+ * Every word's row is divided by its sum c[i] (scaled by the power of two of
+ * its largest entry first; logz gets sum ln c[i] back).  With w / r the
+ * normalised potentials of a word head / of ROOT, the (n-1) x (n-1) matrix
+ * over the words is A[h][d] = -w(d, h), A[d][d] = r(d) + sum_h w(d, h);
+ * single_root (Koo et al. 2007): A[d][d] = sum_h w(d, h) and the first word's
+ * row holds r(.).  Z = det A, the marginals come from the inverse, computed in
+ * fp32 by in-place Gauss-Jordan elimination with partial pivoting (the largest
+ * absolute value of the column, the smallest row among equals); ln Z is summed
+ * in double.  Whether a tree exists is decided on the allowed arcs by
+ * reachability (multi-root: ROOT reaches every word head -> dependent;
+ * single_root: a word with an allowed ROOT arc reaches every word), never on
+ * a pivot; status 2 is also the answer when a pivot is 0 or not finite, the
+ * determinant is not positive or ln Z is not finite.  A marginal is off by
+ * about n * cond_1(A) * 2^-24.
+ * Storage: a graph with n <= GGNN_LAPL_LDS_MAXN keeps its matrix in LDS
+ * ((n-1) rows of (n-1)|1 floats: 157,608 B at 199, 163,264 B of the CU's
+ * 163,840 with the row sums, the pivot record and the permutation; the
+ * reachability bits, 16 KiB, lie in the matrix before it is built), a larger
+ * one in `workspace` (per graph; the tier follows the graph's n).
+ * ggnn_tree_marginals_workspace_bytes(b, v) is 0 for v <= GGNN_LAPL_LDS_MAXN
+ * and b * 4 * (v-1) * ((v-1)|1) above; a smaller workspace is rejected.  Needs
+ * v <= o, v <= GGNN_TREE_MAXV, o <= 1024.  One workgroup per graph, no
+ * atomics, every loop bounded by a function of n, every reduction in a fixed
+ * order.  Stream-ordered, allocation-free, legal under stream capture,
+ * bit-reproducible; booked under the heads kernel kind.  ggnn_arc_confidence
+ * gathers the returned heads' marginals from marg as it is. */
+#define GGNN_LAPL_LDS_MAXN 199
+size_t ggnn_tree_marginals_workspace_bytes(int32_t b, int32_t v);
+int ggnn_tree_marginals(const ggnn_dims* d,        /* b, v used */
+                        const float* probs_head,   /* device [b][v][o] */
+                        int32_t o,
+                        const int32_t* n_nodes,    /* device [b] */
+                        int32_t single_root,       /* 0 / 1 */
+                        float* marg,               /* device [b][v][o] out */
+                        float* logz,               /* device [b] out */
+                        int32_t* scores,           /* device [b][v][o] out, or NULL */
+                        int32_t* status,           /* device [b] out */
+                        void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */

@@ -45,6 +45,27 @@ on their scores) on the same inputs; per line
   marg_err         largest |marg - float64 host form| of the batch
 --epoch then scores the dev set with tree="projective" against
 tree="projective-mbr" (time, UAS, repaired graphs, fetched bytes).
+
+    python tools/ab_tree_decode.py --tree-marginals [--epoch]
+
+alternates, in one process, the plain decode, decode + MST pass, the
+projective marginals, the marginals over all dependency trees
+(ggnn_tree_marginals with scores) and the "mbr" chain built on them (decode,
+marginals, decode of the marginals, MST pass on their scores) on the same
+inputs, and writes its lines to profiles/tree_marginals_ab.jsonl (--out) too;
+per line
+  decode_ms / decode_tree_ms / tree_ms / marg_ms   as above
+  lapl_ms          ggnn_tree_marginals alone
+  mbr_ms           the "mbr" chain;  mbr_extra_ms = mbr_ms - decode_ms
+  mbr_status       graphs whose marginals' arg-max was a tree / was replaced
+                   by the MBR tree / without marginals
+  host_lapl_ms     the fetch + evaluation.tree_marginals_arrays (float64, the
+                   first 32 graphs, scaled to the batch)
+  lapl_err, lapl_err_over_bar   largest |marg - float64 host form| of those
+                   graphs, and against n * cond * 2^-24
+--epoch then scores the dev set with tree=True against tree="mbr" (time, UAS,
+repaired and infeasible graphs, fetched bytes) and parses it with tree="mbr"
+and with tree=True, confidence="nonprojective".
 """
 import argparse
 import json
@@ -233,6 +254,101 @@ def marginals_sizes(torch, sizes):
             print(json.dumps(out), flush=True)
 
 
+def tree_marginals_sizes(torch, sizes, emit):
+    from ggnn_amd import evaluation as E
+    from ggnn_amd.heads import OutputHeads, tree_scores
+    dev = torch.device("cuda", 0)
+    oh = OutputHeads(64)
+    for (b, v, o) in sizes:
+        for regime in ("flat", "peaked", "peaked-projective"):
+            ph, pe, n = batch(b, v, o, 46, regime, seed=b + v)
+            ph_d, pe_d, n_d = (torch.from_numpy(x).to(dev) for x in (ph, pe, n))
+            scores = tree_scores(ph_d, n_d, v)
+
+            def plain():
+                return oh.decode([ph_d, pe_d], n_d)
+
+            def with_tree():
+                pred, _, _ = oh.decode([ph_d, pe_d], n_d)
+                return pred, oh.tree_decode(scores, n_d, pred)
+
+            def projective():
+                return oh.projective_marginals(ph_d, n_d, True)
+
+            def marginals():
+                return oh.tree_marginals(ph_d, n_d, True)
+
+            def mbr():
+                oh.decode([ph_d, pe_d], n_d)
+                marg, _, m_scores, m_status = oh.tree_marginals(ph_d, n_d, True)
+                pred, _, _ = oh.decode([marg, pe_d], n_d)
+                return pred, oh.tree_decode(m_scores, n_d, pred), m_status, m_scores
+
+            calls = 40 if b * v <= 2048 else 10
+            t = alternated(torch, [plain, with_tree, projective, marginals, mbr], calls=calls)
+            out = {"b": b, "v": v, "o": o, "regime": regime}
+            for key, x in zip(("decode_ms", "decode_tree_ms", "marg_ms", "lapl_ms", "mbr_ms"), t):
+                out[key], out[key + "_min"], out[key + "_max"] = x
+            out["tree_ms"] = out["decode_tree_ms"] - out["decode_ms"]
+            out["mbr_extra_ms"] = out["mbr_ms"] - out["decode_ms"]
+            marg, logz, _, m_status = marginals()
+            pred, status, _, m_scores = mbr()
+            torch.cuda.synchronize()
+            tm = time.perf_counter()
+            k = min(b, 32)                                            # (the float64 host form: the first 32 graphs)
+            n_h = n_d[:k].cpu().numpy()
+            h = E.tree_marginals_arrays(ph_d[:k].cpu().numpy(), n_h, True)
+            out["host_lapl_ms"] = (time.perf_counter() - tm) * 1e3 * b / k
+            out["host_lapl_graphs"] = k
+            assert np.array_equal(m_status[:k].cpu().numpy(), h[3])
+            err = np.abs(marg[:k].cpu().numpy().astype(np.float64) - h[0]).max(axis=(1, 2))
+            out["lapl_err"] = float(err.max())
+            out["lapl_err_over_bar"] = float((err / (n_h * h[4] * 2.0 ** -24)).max())
+            out["cond_max"] = float(h[4].max())
+            s_h, p_h = m_scores[:k].cpu().numpy(), pred[:k].cpu().numpy()
+            assert all(E.is_tree(p_h[g, :, 0], n_h[g], True, s_h[g]) for g in range(k))
+            status = np.where(m_status.cpu().numpy() == 1, status.cpu().numpy(), 2)
+            out["mbr_status"] = [int((status == k).sum()) for k in (0, 1, 2)]
+            emit(out)
+
+
+def epoch_tree_mbr(torch, emit):
+    from ggnn_amd import evaluation as E
+    from ggnn_amd.batching import DATA_DIR, TRAIN_WITH_DEV, read_btb_json, wsj_model_sizes
+    from ggnn_amd.model import DenseGGNNChemModel
+    m = DenseGGNNChemModel(params={"hidden_size": 128, "num_timesteps": 2, "batch_size": 20,
+                                   "compact_adjacency": True}, seed=0,
+                           embedding_sizes=dict(loc=32, pos=16, word=32, edge=16), **wsj_model_sizes())
+    data = m.load_data(TRAIN_WITH_DEV["train_file"], False)
+    paths = (("tree", {"tree": True}), ("mbr", {"tree": "mbr"}))
+    for _, kw in paths:
+        m.score_epoch(data, **kw)                                     # both paths warm
+    out = {"what": "score_epoch, 1700 dev sentences, batch 20, untrained model", "tree_s": [], "mbr_s": []}
+    for _ in range(3):                                                # alternating
+        for key, kw in paths:
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            r = m.score_epoch(data, **kw)
+            torch.cuda.synchronize()
+            out[key + "_s"].append(round(time.perf_counter() - t, 4))
+            out[key + "_uas"] = r[2]
+            out[key + "_stats"] = dict(m.decode_stats)
+    emit(out)
+    raw = read_btb_json(os.path.join(DATA_DIR, TRAIN_WITH_DEV["train_file"]))
+    trees = lambda ps: sum(1 for d, p in zip(raw, ps) if len(p) == len(d["node_features"]) - 1
+                           and E.is_tree([-1] + [x[0] for x in p], len(p) + 1, True))
+    t = time.perf_counter()
+    mbr = m.parse(raw, tree="mbr")
+    secs = time.perf_counter() - t
+    mst, conf = m.parse(raw, tree=True, confidence="nonprojective")
+    flat = [c for cs in conf for c in cs]
+    emit({"what": 'parse(dev, tree="mbr") and parse(dev, tree=True, confidence="nonprojective")',
+          "sentences": len(raw), "mbr_single_rooted_trees": trees(mbr), "mst_single_rooted_trees": trees(mst),
+          "parse_mbr_s": round(secs, 3), "confidences": len(flat), "confidence_min": min(flat),
+          "confidence_max": max(flat), "confidence_mean": float(np.mean(flat)),
+          "aligned": all(len(c) == len(p) for c, p in zip(conf, mst))})
+
+
 def epoch_mbr(torch):
     from ggnn_amd.batching import TRAIN_WITH_DEV, wsj_model_sizes
     from ggnn_amd.model import DenseGGNNChemModel
@@ -317,12 +433,30 @@ def main():
     ap.add_argument("--marginals", action="store_true",
                     help="alternate the plain decode, the projective pass, ggnn_projective_marginals and the MBR "
                          "chain (and tree=\"projective\" against tree=\"projective-mbr\" with --epoch)")
+    ap.add_argument("--tree-marginals", action="store_true",
+                    help="alternate the plain decode, the MST pass, ggnn_projective_marginals, ggnn_tree_marginals "
+                         "and the \"mbr\" chain (and tree=True against tree=\"mbr\" with --epoch)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tree_marginals_ab.jsonl"),
+                    help="where --tree-marginals also writes its lines")
     ap.add_argument("--sizes", default="20x40x150,256x128x150")
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "ab_tree_decode.py needs a HIP device"
-    print(json.dumps({"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}), flush=True)
+    head = {"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}
+    print(json.dumps(head), flush=True)
     sizes = [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")]
+    if args.tree_marginals:
+        with open(args.out, "w") as f:
+            def emit(line):
+                text = json.dumps(line)
+                print(text, flush=True)
+                f.write(text + "\n")
+                f.flush()
+            f.write(json.dumps(head) + "\n")
+            tree_marginals_sizes(torch, sizes, emit)
+            if args.epoch:
+                epoch_tree_mbr(torch, emit)
+        return
     if args.marginals:
         marginals_sizes(torch, sizes)
         if args.epoch:
