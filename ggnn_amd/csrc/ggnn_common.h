@@ -131,6 +131,18 @@ DEV u16 lo_limb16(float v) {
   }
   return to_limb<true>(lo_part<true>(v));
 }
+// fp32 residual x - f32(half HALF of the packed f16 pair hpk), hpk = pk<true>(..)
+// of x: one v_fma_mix_f32 reading the f16 half through op_sel (exact, like the
+// convert / subtract pair of lo_part<true>; the consumer is a VALU instruction)
+template <int HALF> DEV float resid16(float x, uint32_t hpk) {
+  if constexpr (GGNN_LIMB_MIX) {
+    float lo;
+    if constexpr (HALF == 0) asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x), "v"(hpk));
+    else asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x), "v"(hpk));
+    return lo;
+  }
+  return x - from_limb<true>((u16)(hpk >> (16 * HALF)));
+}
 template <bool F16, bool MIX = GGNN_LIMB_MIX> DEV frag pk8_lo(const float* x) {
   return make_uint4(pk_lo<F16, MIX>(x[0], x[1]), pk_lo<F16, MIX>(x[2], x[3]), pk_lo<F16, MIX>(x[4], x[5]),
                     pk_lo<F16, MIX>(x[6], x[7]));
@@ -242,6 +254,14 @@ struct Swz {
 DEV uint4 ld16(const void* p) { return *(const uint4*)p; }
 DEV void st16(void* p, uint4 v) { *(uint4*)p = v; }
 DEV frag lds_frag(const char* img, int off) { return ld16(img + off); }
+// ds_read_b64_tr_b16: per group of 16 consecutive lanes, lane 4q + p supplies
+// the (8-byte aligned) address of 4 consecutive 16-bit elements, "row q, columns
+// 4p .. 4p+3"; lane i receives column i of the four rows (row q in element q).
+// EXEC must be all ones: call it from wave-uniform control flow only.
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+DEV v2u32 lds_tr16(const char* p) {
+  return __builtin_bit_cast(v2u32, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p));
+}
 
 // LDS-DMA staging of a [R][NCH] tile of 16-byte chunks (row-major in global)
 // into a Swz<NCH> LDS image.  The DMA destination is lane-linear (wave base +

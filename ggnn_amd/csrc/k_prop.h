@@ -164,6 +164,10 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
   // null: the mask's Philox blocks are drawn here
   dr = drop_resolve(dr);  // (a device-resident key: loaded once)
   TSCLK(3, 0);
+  // phase stamps (GGNN_TS build, tools/ts_probe.py): 0 start, 1 prologue done,
+  // then of the LAST non-empty channel 2 its start, 3 phase a, 4 dbeta product,
+  // 5 phase b, 6 dM^T stores issued; 7 epilogue done
+  TSMARK(3, 0);
   constexpr bool SPLIT = Prec<PREC>::split, F16 = Prec<PREC>::f16;
   using Act = ActT<PREC>;
   constexpr int NS = H / 32, NT = 64 * NS, VT = V / 32, KV = V / 16, KS = H / 16;
@@ -217,47 +221,86 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
 #pragma unroll
     for (int r = 0; r < 16; ++r) adh[jt][r] = bld_p<kPbAux>(rdh, vo, (jt * 32 + acc_row0(r)) * H * 4);
   __syncthreads();
+  TSMARK(3, 1);
 
   for (int ci = 0; ci < nc; ++ci) {
     const int c = chan(ci);
-    // ---- phase a: dM_c^T tile (rows n of this wave), one 32-column j tile at a time
-    v2u32 dq[VT][4];  // f16(dM^T) quad-transposed for the deferred HBM store
-#pragma unroll
-    for (int jt = 0; jt < VT; ++jt) {
-      f32x16 am = splat(0.f);
-#pragma unroll
-      for (int s = 0; s < KV; ++s) {
-        const frag b = lds_frag(abuf, SA::off(jt * 32 + l32, 2 * s + hh));
-        mma_xb<PREC>(am, dxh[s], dxl[s], b);
-      }
-      const int j = jt * 32 + l32;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n0 = ns * 32 + 8 * q + 4 * hh;
-        const uint32_t p0 = pk<F16>(am[4 * q], am[4 * q + 1]), p1 = pk<F16>(am[4 * q + 2], am[4 * q + 3]);
-        const int mo = kimg<V>(j, n0 >> 3) + (n0 & 7) * 2;  // chunk-major dM image
-        *(uint2*)(m_hi + mo) = make_uint2(p0, p1);
+    TSMARK(3, 2);
+    // ---- phase a: dM_c^T tile (rows n of this wave), one 32-column j tile at a time.
+    // Two tiles in flight: tile jt's accumulator is converted and written to the LDS
+    // images in NP pieces, one behind each MFMA of tile jt+1's chain (the wave
+    // issues in order: conversions placed after a whole chain wait for it, and the
+    // next chain waits for them).  The sched_barriers pin that interleaving; left
+    // alone the scheduler hoists all VT chains ahead of the conversions (64
+    // accumulator VGPRs live, spills at 128 x 256).  A_c's fragments run two MFMA
+    // steps ahead of their use.
+    {
+      constexpr int NST = VT * KV;               // MFMA steps (one A_c fragment each)
+      constexpr int NM = SPLIT ? 2 : 1;          // MFMAs per step
+      constexpr int NP = 16 / (KV * NM);         // conversion pieces behind each MFMA (16 per tile)
+      auto lda = [&](int i) { return lds_frag(abuf, SA::off((i / KV) * 32 + l32, 2 * (i % KV) + hh)); };
+      frag bq[2] = {lda(0), lda(NST > 1 ? 1 : 0)};
+      f32x16 am[2];
+      uint32_t pq[2] = {0u, 0u};
+      float lq[2] = {0.f, 0.f};
+      // piece t of a tile: quad q = t >> 2 (registers 4q .. 4q+3: rows n0 .. n0+3 of column j)
+      //   0: the 16-bit limbs -> m_hi    1: e5m2(dM) -> m_lo
+      //   2, 3: the limbs' residuals (one rounding: against the pairs packed in piece 0) 2^F8_M -> m_lo
+      auto piece = [&](int jt, int t, const f32x16& x) {
+        const int q = t >> 2, k = t & 3, j = jt * 32 + l32;
+        const int o = 8 * q + 4 * hh;  // this quad's offset inside the wave's 32 columns
+        const int m8 = kimg<V>(j, 4 * ns + (o >> 4)) + (o & 15);
+        if (k == 0) {
+          const int n0 = ns * 32 + o;
+          pq[0] = pk<F16>(x[4 * q], x[4 * q + 1]);
+          pq[1] = pk<F16>(x[4 * q + 2], x[4 * q + 3]);
+          *(uint2*)(m_hi + kimg<V>(j, n0 >> 3) + (n0 & 7) * 2) = make_uint2(pq[0], pq[1]);  // chunk-major dM image
+        }
         if constexpr (SPLIT) {
           // fp8 correction image (mfma_f8corr's A operand): per row j and 32-column
           // block ns, 4 chunks [e5m2(dM) n 0-15 | n 16-31 | e5m2(dM_lo 2^F8_M) n 0-15 | n 16-31]
-          const int o = 8 * q + 4 * hh;  // this quad's offset inside the wave's 32 columns
-          float lo[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) lo[i] = lo_part<true>(am[4 * q + i]) * (float)(1 << F8_M);
-          const int m8 = kimg<V>(j, 4 * ns + (o >> 4)) + (o & 15);
-          *(uint32_t*)(m_lo + m8) = pk4_bf8(am[4 * q], am[4 * q + 1], am[4 * q + 2], am[4 * q + 3]);
-          *(uint32_t*)(m_lo + m8 + 2 * V * 16) = pk4_bf8(lo[0], lo[1], lo[2], lo[3]);
+          const float sc = (float)(1 << F8_M);
+          if (k == 1) *(uint32_t*)(m_lo + m8) = pk4_bf8(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+          if (k == 2) {
+            lq[0] = resid16<0>(x[4 * q], pq[0]) * sc;
+            lq[1] = resid16<1>(x[4 * q + 1], pq[0]) * sc;
+          }
+          if (k == 3)
+            *(uint32_t*)(m_lo + m8 + 2 * V * 16) =
+                pk4_bf8(lq[0], lq[1], resid16<0>(x[4 * q + 2], pq[1]) * sc, resid16<1>(x[4 * q + 3], pq[1]) * sc);
         }
-        dq[jt][q] = quad_transpose4(p0, p1, l32 & 3);
+      };
+#pragma unroll
+      for (int i = 0; i < NST; ++i) {
+        const int jt = i / KV, s = i % KV;
+        f32x16& acc = am[jt & 1];
+        if (s == 0) acc = splat(0.f);
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+          // (mma_xb's order: the lo limb's product first)
+          if (SPLIT && m == 0) acc = mfma<true>(dxl[s], bq[i & 1], acc);
+          else acc = mfma<F16>(dxh[s], bq[i & 1], acc);
+          if (m == NM - 1 && i + 2 < NST) bq[i & 1] = lda(i + 2);
+          if (jt > 0) {
+#pragma unroll
+            for (int t = (s * NM + m) * NP; t < (s * NM + m + 1) * NP; ++t) piece(jt - 1, t, am[(jt - 1) & 1]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
+#pragma unroll
+      for (int t = 0; t < 16; ++t) piece(VT - 1, t, am[(VT - 1) & 1]);
     }
+    TSMARK(3, 3);
     if (dbp) {
       // dbeta_c[n] = sum_i dX[i][n] deg_c[i] as one more MFMA product: B[i][*] =
       // deg_c[i] (exact integers), every output column holds the sum.  Per-graph
       // partials [b][C][H] (no atomics); reduced over graphs after the last step.
       // (Round 6 tried the column sums of the dM^T accumulators instead -- a lane
       // butterfly, 16 fewer MFMAs per channel and wave -- and the extra live
-      // registers spilled 29-69 VGPRs at 256: not kept.)
+      // registers spilled 29-69 VGPRs at 256: not kept.  Placing the last tile's
+      // conversion pieces behind this product's MFMAs measured no gain either,
+      // profiles/prop_bwd_phase_a_ab.log.)
       const uint4* dg = (const uint4*)(deg + ((long)g * C + c) * V);  // wave-uniform: scalar loads
       f32x16 db = splat(0.f);
 #pragma unroll
@@ -270,6 +313,7 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
       for (int r = 0; r < 16; ++r) v = (r == (l32 & 15)) ? db[r] : v;
       if (l32 < 16) dbp[((long)g * C + c) * H + ns * 32 + acc_row(l32, hh)] = v;
     }
+    TSMARK(3, 4);
     __syncthreads();  // S1: dM images complete, A_c reads done
     // A_{c+1} lands in LDS by DMA while phase b runs (drained by S2)
     if (ci + 1 < nc) glds_tile<ACH, V, NT, kPropAAux>(abuf, ag + (long)chan(ci + 1) * V * V, tid);
@@ -325,33 +369,45 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
       };
       b_pipeline<KS, 2, 1>(ldb, pb);  // rolled ring: measured 3.5 % over b_direct / full unroll (spills)
     }
-    // dM_c^T -> HBM [c][n][N] (weight-gradient operand).  Issued after the last
-    // weight-fragment wait of the channel: vmcnt is in order, so a store ahead of
-    // a load would make that load's wait cover the store too.  The stores then
-    // drain during the next channel's phase a, which has no vector-memory loads.
-    // 16 contiguous bytes per lane: lanes l and l^4 hold neighbouring 4-row
-    // pieces of the same columns for quads q and q+1; one ds_swizzle exchange
-    // gives the even lane both pieces of quad q and the odd lane both of q+1
-    // (8-byte stores are issue-bound: ~7 B/cycle/CU, 16-byte ones about twice
-    // that).  global_store, not buffer_store: the raw-buffer dwordx4 store read
-    // its data VGPRs late (DESIGN.md §4 lessons).
+    TSMARK(3, 5);
+    // dM_c^T -> HBM [c][n][N] (weight-gradient operand), read back from the
+    // 16-bit image m_hi (complete since S1; it holds the bits the stores carry) with
+    // the transposing LDS read, so phase a keeps no copy in registers.  Issued after
+    // the last weight-fragment wait of the channel: vmcnt is in order, so a store
+    // ahead of a load would make that load's wait cover the store too.  The stores
+    // then drain during the next channel's phase a, which has no vector-memory loads.
+    // 16 contiguous bytes (8 j of one n) per lane, (8-byte stores are issue-bound:
+    // ~7 B/cycle/CU, 16-byte ones about twice that); a 32-lane half writes whole
+    // 64-byte lines of 8 n.  Per store s, half hh takes chunk 4 ns + 2 s + hh; its
+    // 16-lane group gb the tile's rows 16 gb .. 16 gb + 15: lane 4q + p of a group
+    // supplies row 8 (p >> 1) + 4 r + q, bytes 8 (p & 1) .. +7 of the chunk, and
+    // lane i receives n = 8 chunk + (i & 7), rows 8 (i >> 3) + 4 r .. + 3.  Group 1
+    // reads its r = 1 rows first: one instruction's 32 lanes of a half then cover
+    // all 64 banks once (rows {0-3, 8-11} and {20-23, 28-31}: no conflict).
+    // global_store, not buffer_store: the raw-buffer dwordx4 store read its data
+    // VGPRs late (DESIGN.md §4 lessons).
     if (dMT) {
-      const bool odd = (l32 >> 2) & 1;
-      u16* dmt = dMT + (long)c * H * N;
+      // lane addresses of the two reads inside a (32 j x 16 n) piece of m_hi and of
+      // the store, recomputed per channel from an opaque copy of the lane id: kept
+      // live across phases a and b they cost five VGPRs there
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      const int gb = (ln >> 4) & 1, i16 = ln & 15, h2 = ln >> 5;
+      const int trx = kimg<V>(16 * gb + 8 * ((i16 >> 1) & 1) + 4 * gb + (i16 >> 2), h2) + 8 * (i16 & 1);
+      const int try_ = trx ^ 64;  // the other 4-row block
+      u16* dmt = dMT + (long)c * H * N + wg_off(ns * 32 + 8 * h2 + (i16 & 7), rowg + 16 * gb + 8 * (i16 >> 3), H);
 #pragma unroll
       for (int jt = 0; jt < VT; ++jt)
 #pragma unroll
-        for (int qp = 0; qp < 4; qp += 2) {
-          const v2u32 mine = odd ? dq[jt][qp + 1] : dq[jt][qp];
-          const v2u32 send = odd ? dq[jt][qp] : dq[jt][qp + 1];
-          const uint32_t r0 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)send.x, 0x101F);  // lane ^ 4
-          const uint32_t r1 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)send.y, 0x101F);
+        for (int s = 0; s < 2; ++s) {
+          const char* src = m_hi + kimg<V>(jt * 32, 4 * ns + 2 * s);
+          const v2u32 x = lds_tr16(src + trx), y = lds_tr16(src + try_);
           typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-          const u32x4v out = odd ? u32x4v{r0, r1, mine.x, mine.y} : u32x4v{mine.x, mine.y, r0, r1};
-          const int nn = ns * 32 + 8 * (qp + (odd ? 1 : 0)) + 4 * hh + (l32 & 3);
-          __builtin_nontemporal_store(out, (u32x4v*)(dmt + wg_off(nn, rowg + jt * 32 + 8 * (l32 >> 3), H)));
+          const u32x4v out = gb ? u32x4v{y.x, y.y, x.x, x.y} : u32x4v{x.x, x.y, y.x, y.y};
+          __builtin_nontemporal_store(out, (u32x4v*)(dmt + wg_off(16 * s, jt * 32, H)));
         }
     }
+    TSMARK(3, 6);
     __syncthreads();  // S2: dM image reads done, A_{c+1} staged
   }
   const rsrc_t rdo = mkrsrc(dh_out + rowg * H, V * H * 4);
@@ -393,5 +449,6 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
         for (int q = tid; q < H; q += NT) dbp[((long)g * C + c) * H + q] = 0.f;
     }
   }
+  TSMARK(3, 7);
   TSCLK(3, 1);
 }

@@ -37,7 +37,9 @@ assert lib.ggnn_dbg_ts(buf.ctypes.data_as(ctypes.c_void_p)) == 0
 names = {0: ("gru_fwd", 512, ["stage", "passA", "rh", "passB", "blend+st"]),
          1: ("gru_bwd", 512, ["ph1", "prod1", "ph2", "prod2+st"]),
          2: ("fwd_fused (last t)", 256, ["msg", "X out", "passA", "rh", "passB", "blend"]),
-         3: ("prop_bwd", 256, ["stage", "chan loop", "dh out"])}
+         # stamps 2-6 are those of the graph's LAST non-empty channel
+         3: ("prop_bwd", 256, ["stage", "channels before the last", "phase a", "dbeta", "S1 + phase b", "dMT stores",
+                               "S2 + dh out"])}
 for k, (nm, nwg, phases) in names.items():
     nwg = int((buf[k, :, 0] != 0).sum())
     if nwg == 0:
