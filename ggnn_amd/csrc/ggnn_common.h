@@ -263,37 +263,56 @@ DEV v2u32 lds_tr16(const char* p) {
   return __builtin_bit_cast(v2u32, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p));
 }
 
+// LDS-DMA of 16 B per lane in inline asm: invisible to hipcc's waitcnt pass,
+// which would otherwise wait vmcnt(0) before every ds_read of the ring (it
+// cannot tell the ring slots apart); completion is counted by hand by the caller.
+// NTEMP: the nontemporal cache policy (kNT).
+template <bool NTEMP = false>
+DEV void glds16_asm(const void* gsrc, const char* lds_dst) {
+  unsigned keep;
+  const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
+  if constexpr (NTEMP)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(dst)
+                 : "memory");
+  else
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(dst)
+                 : "memory");
+}
+
 // LDS-DMA staging of a [R][NCH] tile of 16-byte chunks (row-major in global)
 // into a Swz<NCH> LDS image.  The DMA destination is lane-linear (wave base +
 // 16*lane), so the swizzle goes on the SOURCE address: LDS slot (row, pc)
 // receives logical chunk pc ^ (row & M), the same involution Swz::off reads
 // with.  No VGPR staging; completion is on vmcnt (a __syncthreads drains it).
-template <int NCH, int R, int NT, int AUX = 0>
+// ASM: through glds16_asm, for a tile staged while a rolled loop streams
+// fragments from global memory and LDS.  The waitcnt pass then sees no pending
+// LDS write: it neither drains vmcnt before the loop's ds_reads nor counts these
+// DMAs, so its vmcnt(N) for a younger load is stricter than needed, never looser
+// (the counter retires in order).  The caller waits for the DMAs by hand before
+// the barrier that publishes the tile.
+template <int NCH, int R, int NT, int AUX = 0, bool ASM = false>
 DEV void glds_tile(char* lds, const u16* src, int tid) {
   typedef Swz<NCH> S;
   constexpr int TOT = R * NCH;
+  // (ASM: lane addresses from an opaque copy of the thread id; hoisted out of the
+  // caller's loops they would stay live in VGPRs between the calls)
+  if constexpr (ASM) asm volatile("" : "+v"(tid));
   const int lane = tid & 63;
 #pragma unroll
   for (int p = 0; p < (TOT + NT - 1) / NT; ++p) {
     const int qb = p * NT + (tid & ~63);  // wave-uniform first slot
     if (qb < TOT) {
       const int q = qb + lane, row = q / NCH, pc = q % NCH;
-      __builtin_amdgcn_global_load_lds((const void*)(src + (row * NCH + (pc ^ (row & S::M))) * 8),
-                                       (__attribute__((address_space(3))) void*)(lds + qb * 16), 16, 0, AUX);
+      const u16* g = src + (row * NCH + (pc ^ (row & S::M))) * 8;
+      if constexpr (ASM) glds16_asm<(AUX & 2) != 0>(g, lds + qb * 16);
+      else
+        __builtin_amdgcn_global_load_lds((const void*)g, (__attribute__((address_space(3))) void*)(lds + qb * 16), 16, 0, AUX);
     }
   }
-}
-
-// LDS-DMA of 16 B per lane in inline asm: invisible to hipcc's waitcnt pass,
-// which would otherwise wait vmcnt(0) before every ds_read of the ring (it
-// cannot tell the ring slots apart); completion is counted by hand below.
-DEV void glds16_asm(const void* gsrc, const char* lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(dst)
-               : "memory");
 }
 
 // B-operand fragment of a packed matrix: [strip][kstep][64 lanes][8] limbs

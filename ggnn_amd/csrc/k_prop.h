@@ -226,6 +226,17 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
   for (int ci = 0; ci < nc; ++ci) {
     const int c = chan(ci);
     TSMARK(3, 2);
+    // Split mode: one dword of each 128-byte line of A_{c+1} is loaded here, so that the
+    // tile's DMA (after S1) finds it in L2: phase b's first weight-fragment wait covers
+    // that DMA (vmcnt retires in order), and from HBM it stalled every wave there (a
+    // channel that stages a tile took 1.4 us longer than the last one, which stages none:
+    // profiles/prop_bwd_phase_b_before.log; the touch's A/B: prop_bwd_phase_b_ab.log).  The
+    // value is not used; it is consumed after phase b, where the load has long retired.
+    unsigned pf = 0;
+    if constexpr (SPLIT) {
+      if (ci + 1 < nc && tid < A_BYTES / 128)
+        pf = ((const unsigned*)(ag + (long)chan(ci + 1) * V * V))[tid * 32];
+    }
     // ---- phase a: dM_c^T tile (rows n of this wave), one 32-column j tile at a time.
     // Two tiles in flight: tile jt's accumulator is converted and written to the LDS
     // images in NP pieces, one behind each MFMA of tile jt+1's chain (the wave
@@ -315,8 +326,13 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
     }
     TSMARK(3, 4);
     __syncthreads();  // S1: dM images complete, A_c reads done
-    // A_{c+1} lands in LDS by DMA while phase b runs (drained by S2)
-    if (ci + 1 < nc) glds_tile<ACH, V, NT, kPropAAux>(abuf, ag + (long)chan(ci + 1) * V * V, tid);
+    // A_{c+1} lands in LDS by DMA while phase b runs.  Split mode: issued from inline
+    // asm, so the waitcnt pass sees no pending LDS write (with one it waits vmcnt(0) at
+    // the top of every k-block of the rolled loop below, draining the weight fragments
+    // just issued); waited for by hand after the loop, published by S2
+    if (ci + 1 < nc) {
+      glds_tile<ACH, V, NT, kPropAAux, SPLIT>(abuf, ag + (long)chan(ci + 1) * V * V, tid);
+    }
     // ---- phase b: dh[j][k] += sum_n dM_c[j][n] W_c^T[n][k]
     const u16* wt = WTp + (size_t)c * H * H;
     // Split mode: dM and W_c^T both as hi + lo (round 5's hi-only W_c^T reached
@@ -337,17 +353,21 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
         const uint4* f = (const uint4*)(w8 + ((size_t)(ns * (KS / 2) + kb) * 64 + lane) * 32);
         return F2{f[0], f[1]};
       };
+      constexpr int NKB = KS / 2;
+      typedef std::integral_constant<bool, false> NotLast;
+      typedef std::integral_constant<bool, true> Last;
+      // each half waits only for its own fragment (vmcnt(2): the other half's two loads
+      // stay in flight); the last k-block is peeled and loads nothing
       F2 rh = ld_h(0), rf = ld_f(0);
-#pragma unroll 1
-      for (int kb = 0; kb < KS / 2; ++kb) {
-        const int kn = min(kb + 1, KS / 2 - 1);
+      auto blk = [&](int kb, auto last) {
+        constexpr bool LAST = decltype(last)::value;
 #pragma unroll
         for (int jt = 0; jt < VT; ++jt) {
           const int row = jt * 32 + l32;
           adh[jt] = mfma<true>(lds_frag(m_hi, kimg<V>(row, 4 * kb + hh)), rh.a, adh[jt]);
           adh[jt] = mfma<true>(lds_frag(m_hi, kimg<V>(row, 4 * kb + 2 + hh)), rh.b, adh[jt]);
         }
-        rh = ld_h(kn);
+        if (!LAST) rh = ld_h(kb + 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int jt = 0; jt < VT; ++jt) {
@@ -355,9 +375,16 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
           const uint4 p0 = ld16(m_lo + kimg<V>(row, 4 * kb + 2 * hh)), p1 = ld16(m_lo + kimg<V>(row, 4 * kb + 2 * hh + 1));
           adh[jt] = mfma_f8corr(p0, p1, rf.a, rf.b, adh[jt]);
         }
-        rf = ld_f(kn);
+        if (!LAST) rf = ld_f(kb + 1);
         __builtin_amdgcn_sched_barrier(0);
-      }
+      };
+#pragma unroll 1
+      for (int kb = 0; kb < NKB - 1; ++kb) blk(kb, NotLast());
+      blk(NKB - 1, Last());
+      // (register-only MFMAs may be sunk past the stores and S2 into the next channel,
+      // and the last fp8 fragment's wait with them: it would then cover the stores)
+#pragma unroll
+      for (int jt = 0; jt < VT; ++jt) asm volatile("" : "+v"(adh[jt])::"memory");
     } else {
       auto ldb = [&](int ks) { return F2{frag_ld(wt, ns, ks, KS, lane), frag{}}; };
       auto pb = [&](int ks, const F2& w) {
@@ -369,13 +396,18 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
       };
       b_pipeline<KS, 2, 1>(ldb, pb);  // rolled ring: measured 3.5 % over b_direct / full unroll (spills)
     }
+    if constexpr (SPLIT) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // A_{c+1}'s DMAs (older than every fragment load: retired long ago)
+      asm volatile("" ::"v"(pf));
+    }
     TSMARK(3, 5);
     // dM_c^T -> HBM [c][n][N] (weight-gradient operand), read back from the
     // 16-bit image m_hi (complete since S1; it holds the bits the stores carry) with
     // the transposing LDS read, so phase a keeps no copy in registers.  Issued after
     // the last weight-fragment wait of the channel: vmcnt is in order, so a store
     // ahead of a load would make that load's wait cover the store too.  The stores
-    // then drain during the next channel's phase a, which has no vector-memory loads.
+    // then drain during the next channel's phase a, whose only vector-memory loads are
+    // the split mode's touch of A_{c+2}'s lines (consumed after phase b, not there).
     // 16 contiguous bytes (8 j of one n) per lane, (8-byte stores are issue-bound:
     // ~7 B/cycle/CU, 16-byte ones about twice that); a 32-lane half writes whole
     // 64-byte lines of 8 n.  Per store s, half hh takes chunk 4 ns + 2 s + hh; its
