@@ -288,19 +288,10 @@ DEV void glds16_asm(const void* gsrc, const char* lds_dst) {
 // 16*lane), so the swizzle goes on the SOURCE address: LDS slot (row, pc)
 // receives logical chunk pc ^ (row & M), the same involution Swz::off reads
 // with.  No VGPR staging; completion is on vmcnt (a __syncthreads drains it).
-// ASM: through glds16_asm, for a tile staged while a rolled loop streams
-// fragments from global memory and LDS.  The waitcnt pass then sees no pending
-// LDS write: it neither drains vmcnt before the loop's ds_reads nor counts these
-// DMAs, so its vmcnt(N) for a younger load is stricter than needed, never looser
-// (the counter retires in order).  The caller waits for the DMAs by hand before
-// the barrier that publishes the tile.
-template <int NCH, int R, int NT, int AUX = 0, bool ASM = false>
+template <int NCH, int R, int NT, int AUX = 0>
 DEV void glds_tile(char* lds, const u16* src, int tid) {
   typedef Swz<NCH> S;
   constexpr int TOT = R * NCH;
-  // (ASM: lane addresses from an opaque copy of the thread id; hoisted out of the
-  // caller's loops they would stay live in VGPRs between the calls)
-  if constexpr (ASM) asm volatile("" : "+v"(tid));
   const int lane = tid & 63;
 #pragma unroll
   for (int p = 0; p < (TOT + NT - 1) / NT; ++p) {
@@ -308,10 +299,43 @@ DEV void glds_tile(char* lds, const u16* src, int tid) {
     if (qb < TOT) {
       const int q = qb + lane, row = q / NCH, pc = q % NCH;
       const u16* g = src + (row * NCH + (pc ^ (row & S::M))) * 8;
-      if constexpr (ASM) glds16_asm<(AUX & 2) != 0>(g, lds + qb * 16);
-      else
-        __builtin_amdgcn_global_load_lds((const void*)g, (__attribute__((address_space(3))) void*)(lds + qb * 16), 16, 0, AUX);
+      __builtin_amdgcn_global_load_lds((const void*)g, (__attribute__((address_space(3))) void*)(lds + qb * 16), 16, 0, AUX);
     }
+  }
+}
+
+// The same tile through registers, for a kernel whose LDS buffer is still being
+// read while the tile should already be on its way: tile_ld loads the chunks of
+// this thread's LDS slots (slot q = p NT + tid; exactly the source addresses the
+// DMA of glds_tile reads), tile_st writes them to those slots later.  The LDS
+// image is byte for byte the DMA's.  (R NCH + NT - 1) / NT x 4 VGPRs in between.
+template <int NCH, int R, int NT, int AUX = 0>
+DEV void tile_ld(uint4 (&r)[(R * NCH + NT - 1) / NT], const u16* src, int tid) {
+  typedef Swz<NCH> S;
+  typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
+  constexpr int TOT = R * NCH;
+  // (lane addresses from an opaque copy of the thread id: hoisted out of the caller's
+  // loops they would stay live in VGPRs between the calls)
+  asm volatile("" : "+v"(tid));
+#pragma unroll
+  for (int p = 0; p < (TOT + NT - 1) / NT; ++p) {
+    const int q = p * NT + tid;
+    if ((p + 1) * NT <= TOT || q < TOT) {  // (a whole pass: no branch)
+      const int row = q / NCH, pc = q % NCH;
+      const u16* g = src + (row * NCH + (pc ^ (row & S::M))) * 8;
+      if constexpr ((AUX & 2) != 0) r[p] = __builtin_bit_cast(uint4, __builtin_nontemporal_load((const u32x4v*)g));
+      else r[p] = ld16(g);
+    }
+  }
+}
+template <int NCH, int R, int NT>
+DEV void tile_st(char* lds, const uint4 (&r)[(R * NCH + NT - 1) / NT], int tid) {
+  constexpr int TOT = R * NCH;
+  asm volatile("" : "+v"(tid));
+#pragma unroll
+  for (int p = 0; p < (TOT + NT - 1) / NT; ++p) {
+    const int q = p * NT + tid;
+    if ((p + 1) * NT <= TOT || q < TOT) st16(lds + q * 16, r[p]);
   }
 }
 

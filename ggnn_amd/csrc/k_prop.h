@@ -164,9 +164,10 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
   // null: the mask's Philox blocks are drawn here
   dr = drop_resolve(dr);  // (a device-resident key: loaded once)
   TSCLK(3, 0);
-  // phase stamps (GGNN_TS build, tools/ts_probe.py): 0 start, 1 prologue done,
-  // then of the LAST non-empty channel 2 its start, 3 phase a, 4 dbeta product,
-  // 5 phase b, 6 dM^T stores issued; 7 epilogue done
+  // phase stamps (GGNN_TS build, tools/ts_probe.py), in the order they are taken:
+  // 0 start, 4 dX^T fragments built and the dbeta product done, 1 prologue barrier
+  // passed (first A tile, keep bits), then of the LAST non-empty channel 2 its
+  // start, 3 phase a, 5 S1 + phase b, 6 dM^T stores issued; 7 epilogue done
   TSMARK(3, 0);
   constexpr bool SPLIT = Prec<PREC>::split, F16 = Prec<PREC>::f16;
   using Act = ActT<PREC>;
@@ -215,27 +216,70 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
   const bool drop = dr.thr != 0 && tm >= 0;
   uint2 kb = make_uint2(0u, 0u);
   if (drop && sbits) kb = sbits[((long)tm * gridDim.x + g) * NT + tid];
+  if (dbp) {
+    // dbeta_c[n] = sum_i dX[i][n] deg_c[i] as one more MFMA product, once per launch:
+    // output column l32 of group grp belongs to the graph's non-empty channel
+    // chan(32 grp + l32), B[i][l32] = deg_c[i] (exact integers; zeros past nc).  MFMA
+    // columns are independent, so each partial has the bits of a product whose 32
+    // columns all carried one channel's deg (what ran once per channel, between phase
+    // a and S1, until this was moved: 1.4-1.7 us of every channel's chain,
+    // profiles/prop_bwd_launch_before.log).  Here it runs while the first A tile is
+    // in flight.  Per-graph partials [b][C][H] (no atomics); reduced over graphs
+    // after the last step.
+    // (Round 6 tried the column sums of the dM^T accumulators instead -- a lane
+    // butterfly, 16 fewer MFMAs per channel and wave -- and the extra live
+    // registers spilled 29-69 VGPRs at 256: not kept.)
+#pragma unroll 1
+    for (int grp = 0; 32 * grp < nc; ++grp) {
+      const int li = 32 * grp + l32;
+      const bool live = li < nc;
+      // (a column past the list's end loads the degrees of the list's first channel and
+      // drops them: in bounds, and no branch around the loads)
+      const int c = chan(live ? li : 0);
+      const u16* dg = deg + ((long)g * C + c) * V + 8 * hh;
+      frag dq[KV];
+#pragma unroll
+      for (int ss = 0; ss < KV; ++ss) {
+        const frag d = ld16(dg + 16 * ss);
+        dq[ss] = live ? d : make_uint4(0, 0, 0, 0);
+      }
+      f32x16 db = splat(0.f);
+#pragma unroll
+      for (int ss = 0; ss < KV; ++ss) mma_xb<PREC>(db, dxh[ss], dxl[ss], dq[ss]);
+      // lane (l32, hh) holds rows 8 q + 4 hh .. + 3 of its channel in registers 4 q .. 4 q + 3
+      if (live) {
+        float* o = dbp + ((long)g * C + c) * H + ns * 32 + 4 * hh;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *(float4*)(o + 8 * q) = make_float4(db[4 * q], db[4 * q + 1], db[4 * q + 2], db[4 * q + 3]);
+      }
+    }
+  }
+  TSMARK(3, 4);
+  __syncthreads();  // dX^T fragments built, first A tile and keep bits landed
+  TSMARK(3, 1);
+  // dL/dh_t, the C operand of phase b: loaded behind the barrier, so that the barrier's
+  // vmcnt(0) does not wait for it; it lands under channel 0's phase a and is first
+  // waited for in phase b (nothing in phase a waits on vmcnt).  With nc == 0 it passes
+  // straight to the epilogue.
   f32x16 adh[VT];
 #pragma unroll
   for (int jt = 0; jt < VT; ++jt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) adh[jt][r] = bld_p<kPbAux>(rdh, vo, (jt * 32 + acc_row0(r)) * H * 4);
-  __syncthreads();
-  TSMARK(3, 1);
 
   for (int ci = 0; ci < nc; ++ci) {
     const int c = chan(ci);
     TSMARK(3, 2);
-    // Split mode: one dword of each 128-byte line of A_{c+1} is loaded here, so that the
-    // tile's DMA (after S1) finds it in L2: phase b's first weight-fragment wait covers
-    // that DMA (vmcnt retires in order), and from HBM it stalled every wave there (a
-    // channel that stages a tile took 1.4 us longer than the last one, which stages none:
-    // profiles/prop_bwd_phase_b_before.log; the touch's A/B: prop_bwd_phase_b_ab.log).  The
-    // value is not used; it is consumed after phase b, where the load has long retired.
-    unsigned pf = 0;
+    // Split mode: A_{c+1} is loaded into registers here (NAP x 16 bytes per lane, the
+    // source addresses of the tile's DMA) and flies under phase a; LDS is full, so it is
+    // written to abuf only after S1, when every wave is done with A_c.  Phase b then has
+    // nothing but its weight fragments on vmcnt.  (Until this, the tile went out as an
+    // LDS-DMA after S1, its lines touched into L2 from here, and phase b's first fragment
+    // wait covered it: profiles/prop_bwd_phase_b_ab.log, prop_bwd_launch_ab.log.)
+    constexpr int NAP = (V * ACH + NT - 1) / NT;
+    uint4 an[NAP] = {};
     if constexpr (SPLIT) {
-      if (ci + 1 < nc && tid < A_BYTES / 128)
-        pf = ((const unsigned*)(ag + (long)chan(ci + 1) * V * V))[tid * 32];
+      if (ci + 1 < nc) tile_ld<ACH, V, NT, kPropAAux>(an, ag + (long)chan(ci + 1) * V * V, tid);
     }
     // ---- phase a: dM_c^T tile (rows n of this wave), one 32-column j tile at a time.
     // Two tiles in flight: tile jt's accumulator is converted and written to the LDS
@@ -303,35 +347,14 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
       for (int t = 0; t < 16; ++t) piece(VT - 1, t, am[(VT - 1) & 1]);
     }
     TSMARK(3, 3);
-    if (dbp) {
-      // dbeta_c[n] = sum_i dX[i][n] deg_c[i] as one more MFMA product: B[i][*] =
-      // deg_c[i] (exact integers), every output column holds the sum.  Per-graph
-      // partials [b][C][H] (no atomics); reduced over graphs after the last step.
-      // (Round 6 tried the column sums of the dM^T accumulators instead -- a lane
-      // butterfly, 16 fewer MFMAs per channel and wave -- and the extra live
-      // registers spilled 29-69 VGPRs at 256: not kept.  Placing the last tile's
-      // conversion pieces behind this product's MFMAs measured no gain either,
-      // profiles/prop_bwd_phase_a_ab.log.)
-      const uint4* dg = (const uint4*)(deg + ((long)g * C + c) * V);  // wave-uniform: scalar loads
-      f32x16 db = splat(0.f);
-#pragma unroll
-      for (int ss = 0; ss < KV; ++ss) {
-        const uint4 d0 = dg[2 * ss], d1 = dg[2 * ss + 1];
-        mma_xb<PREC>(db, dxh[ss], dxl[ss], hh ? d1 : d0);
-      }
-      float v = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) v = (r == (l32 & 15)) ? db[r] : v;
-      if (l32 < 16) dbp[((long)g * C + c) * H + ns * 32 + acc_row(l32, hh)] = v;
-    }
-    TSMARK(3, 4);
     __syncthreads();  // S1: dM images complete, A_c reads done
-    // A_{c+1} lands in LDS by DMA while phase b runs.  Split mode: issued from inline
-    // asm, so the waitcnt pass sees no pending LDS write (with one it waits vmcnt(0) at
-    // the top of every k-block of the rolled loop below, draining the weight fragments
-    // just issued); waited for by hand after the loop, published by S2
+    // A_{c+1} into abuf, published by S2.  Split mode: from the registers loaded at the top
+    // of the channel (ds_write_b128, the slots the DMA would fill; the compiler's vmcnt(0)
+    // in front of it also covers the previous channel's dM^T stores, a phase a old by
+    // now).  16-bit modes: by DMA while phase b runs, as before
     if (ci + 1 < nc) {
-      glds_tile<ACH, V, NT, kPropAAux, SPLIT>(abuf, ag + (long)chan(ci + 1) * V * V, tid);
+      if constexpr (SPLIT) tile_st<ACH, V, NT>(abuf, an, tid);
+      else glds_tile<ACH, V, NT, kPropAAux>(abuf, ag + (long)chan(ci + 1) * V * V, tid);
     }
     // ---- phase b: dh[j][k] += sum_n dM_c[j][n] W_c^T[n][k]
     const u16* wt = WTp + (size_t)c * H * H;
@@ -396,10 +419,6 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
       };
       b_pipeline<KS, 2, 1>(ldb, pb);  // rolled ring: measured 3.5 % over b_direct / full unroll (spills)
     }
-    if constexpr (SPLIT) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // A_{c+1}'s DMAs (older than every fragment load: retired long ago)
-      asm volatile("" ::"v"(pf));
-    }
     TSMARK(3, 5);
     // dM_c^T -> HBM [c][n][N] (weight-gradient operand), read back from the
     // 16-bit image m_hi (complete since S1; it holds the bits the stores carry) with
@@ -407,7 +426,7 @@ k_prop_bwd(const ActT<PREC>* __restrict__ dXT, const u16* __restrict__ AbT, cons
     // the last weight-fragment wait of the channel: vmcnt is in order, so a store
     // ahead of a load would make that load's wait cover the store too.  The stores
     // then drain during the next channel's phase a, whose only vector-memory loads are
-    // the split mode's touch of A_{c+2}'s lines (consumed after phase b, not there).
+    // the split mode's loads of A_{c+2} (consumed after S1, not there).
     // 16 contiguous bytes (8 j of one n) per lane, (8-byte stores are issue-bound:
     // ~7 B/cycle/CU, 16-byte ones about twice that); a 32-lane half writes whole
     // 64-byte lines of 8 n.  Per store s, half hh takes chunk 4 ns + 2 s + hh; its

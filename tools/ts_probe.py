@@ -37,14 +37,17 @@ assert lib.ggnn_dbg_ts(buf.ctypes.data_as(ctypes.c_void_p)) == 0
 names = {0: ("gru_fwd", 512, ["stage", "passA", "rh", "passB", "blend+st"]),
          1: ("gru_bwd", 512, ["ph1", "prod1", "ph2", "prod2+st"]),
          2: ("fwd_fused (last t)", 256, ["msg", "X out", "passA", "rh", "passB", "blend"]),
-         # stamps 2-6 are those of the graph's LAST non-empty channel
-         3: ("prop_bwd", 256, ["stage", "channels before the last", "phase a", "dbeta", "S1 + phase b", "dMT stores",
-                               "S2 + dh out"])}
+         # stamps 2-6 are those of the graph's LAST non-empty channel; stamp 4 (the dbeta
+         # product, once per launch) is taken in the prologue, between stamps 0 and 1
+         3: ("prop_bwd", 256, ["dXT frags + dbeta", "barrier (A tile)", "channels before the last", "phase a",
+                               "S1 + phase b", "dMT stores", "S2 + dh out"])}
+# the order in which a kernel takes its stamps, where it is not 0, 1, 2, ...
+order = {3: [0, 4, 1, 2, 3, 5, 6, 7]}
 for k, (nm, nwg, phases) in names.items():
     nwg = int((buf[k, :, 0] != 0).sum())
     if nwg == 0:
         continue
-    t = buf[k, :nwg, :len(phases) + 1].astype(np.int64)
+    t = buf[k][:nwg][:, order.get(k, list(range(len(phases) + 1)))].astype(np.int64)
     t0 = t[:, 0].min()
     t = (t - t0) * 0.01  # us
     d = np.diff(t, axis=1)
