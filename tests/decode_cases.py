@@ -13,14 +13,17 @@ def _torch():
     return torch
 
 
-def _synthetic_model(graphs, hidden=64, **params):
+def _synthetic_model(graphs, hidden=64, device=None, seed=0, **params):
     """hidden 64: the general path; 128: the specialised kernels and the
-    fused forward (the embedding concat is 16 + 16 + 8 + 24 wide)."""
+    fused forward (the embedding concat is 16 + 16 + 8 + 24 wide).
+    device="cpu": the same variables, seeds and feeds on a machine without a
+    GPU (no step can run there).  seed: of the initial variables and of the
+    Philox seeds the model draws."""
     from ggnn_amd.model import DenseGGNNChemModel
     return DenseGGNNChemModel(params={"hidden_size": hidden, "num_timesteps": 2, "batch_size": 5,
                                       "compact_adjacency": True, "hip_graphs": graphs, **params},
                               num_edge_types=6, output_size_edges=12, pos_size=46, vocab_size=200, max_nodes=40,
-                              seed=0, embedding_sizes=dict(loc=16, pos=8, word=24, edge=16))
+                              seed=seed, device=device, embedding_sizes=dict(loc=16, pos=8, word=24, edge=16))
 
 
 def _synthetic_raw():

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import ggnn_oracle as O
+import trajectory_cases as TC
 
 pytestmark = pytest.mark.gpu
 
@@ -138,43 +139,11 @@ def _check_train_step(m, fd, adam=True):
     before = [p.detach().cpu().numpy().astype(np.float64) for p in params]
     loss = m.train_step(fd)
     after = [p.detach().cpu().numpy() for p in params]
-    # ---- oracle
-    W = m.weights
-    nm = {id(p): i for i, p in enumerate(params)}
-    P = lambda t: before[nm[id(t)]]
-    h = m.params["hidden_size"]
-    wi = np.asarray(fd["word_inputs"]).astype(np.int64)
-    segs = [(P(W["loc_embeddings"]), 0), (P(W["pos_embeddings"]), 1), (P(W["word_embeddings"]), 2),
-            (P(W["loc_embeddings"]), 3)]
-    e = m.last_embed
-    h0 = O.embed_forward(segs, wi, h, e["keep"], e["seed"])
-    w64 = {"edge_weights": P(W["edge_weights"]), "edge_biases": P(W["edge_biases"])}
-    w64.update({k: P(t) for k, t in W["node_gru"].items()})
-    if fd.get("adjacency_matrix") is None:
-        from ggnn_amd.batching import graph_to_adj_mat_bd
-        A = np.stack([graph_to_adj_mat_bd(g, fd["num_vertices"], m.num_edge_types) for g in fd["adjacency_edges"]])
-    else:
-        A = np.asarray(fd["adjacency_matrix"], np.float64)
-    dr = m.last_dropout
-    hT, caches = O.forward(A, h0, w64, m.params["num_timesteps"],
-                           dropout=dict(edge_keep=dr["edge_keep"], state_keep=dr["state_keep"], seed=dr["seed"]))
-    b, v = fd["num_graphs"], fd["num_vertices"]
-    o, oe = m.params["output_size"], m.output_size_edges
-    g0, ge = W["regression_gate_task0"], W["regression_gate_task_edges0"]
-    heads = [dict(W=P(g0["weights"][0]), b=P(g0["biases"][0]),
-                  labels=np.asarray(fd["target_values_head"], np.float64).reshape(b, v, o)),
-             dict(W=P(ge["weights"][0]), b=P(ge["biases"][0]),
-                  labels=np.asarray(fd["target_values_edges"], np.float64).reshape(b, v, oe))]
-    hd = m.last_heads
-    probs, losses = O.heads_forward(hT, h0, heads, hd["keep"], hd["seed"], hd["target_num"])
-    assert abs(float(loss.detach()) - sum(losses)) <= TOL * abs(sum(losses))
-    dWs, dbs, dhT, dh0_heads = O.heads_backward(hT, h0, heads, probs, hd["keep"], hd["seed"], hd["target_num"])
-    gp = O.backward(A, dhT, caches, w64)
-    dts, sq = O.embed_backward(segs, wi, h, dh0_heads + gp["h0"], e["keep"], e["seed"])
-    grads = [gp["edge_weights"], gp["edge_biases"]] + [gp[k] for k in ("gates_kernel", "gates_bias", "candidate_kernel",
-                                                                      "candidate_bias")]
-    grads += [dts[0] + dts[3], dts[1], dts[2], dWs[0], dbs[0], dWs[1], dbs[1]]
-    sqn = [None] * 6 + [sq[0] + sq[3], sq[1], sq[2]] + [None] * 4
+    # ---- oracle (trajectory_cases.oracle_step: the composition this helper always made)
+    o = TC.oracle_step(TC.spec_of(m), before, fd, dict(embed=m.last_embed, path=m.last_dropout, heads=m.last_heads))
+    assert abs(float(loss.detach()) - o["loss"]) <= TOL * abs(o["loss"])
+    grads, gp = o["grads"], o["gp"]
+    sqn = [None] * 6 + list(o["sq"]) + [None] * 4
     # TF1 Adam step 1 with clip_by_norm (IndexedSlices norm for the tables)
     lr, clip = m.params["learning_rate"], m.params["clamp_gradient_norm"]
     lr_t = lr * np.sqrt(1 - 0.999) / (1 - 0.9)
