@@ -36,6 +36,7 @@ EXPORTED = (
     "ggnn_projective_decode_workspace_bytes", "ggnn_projective_decode",
     "ggnn_projective_marginals_workspace_bytes", "ggnn_projective_marginals", "ggnn_arc_confidence",
     "ggnn_tree_marginals_workspace_bytes", "ggnn_tree_marginals",
+    "ggnn_tree_loss_workspace_bytes", "ggnn_tree_loss", "ggnn_tree_loss_dev",
 )
 DECODE_COUNTS = 5   # include/ggnn.h GGNN_DECODE_COUNTS: n_kept, las, uas, lab, regular
 TREE_MAXV = 256                # include/ggnn.h GGNN_TREE_MAXV
@@ -157,6 +158,14 @@ def load(path: str | None = None) -> ctypes.CDLL:
         lib.ggnn_tree_marginals.restype = _I
         lib.ggnn_tree_marginals.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
                                             ctypes.c_size_t, _P]
+        lib.ggnn_tree_loss_workspace_bytes.restype = ctypes.c_size_t
+        lib.ggnn_tree_loss_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        lib.ggnn_tree_loss.restype = _I
+        lib.ggnn_tree_loss.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32, F,
+                                       _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+        lib.ggnn_tree_loss_dev.restype = _I
+        lib.ggnn_tree_loss_dev.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32, _P,
+                                           _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
         lib.ggnn_arc_confidence.restype = _I
         lib.ggnn_arc_confidence.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, _P, _P]
         lib.ggnn_dbg_gemm.restype = _I

@@ -25,6 +25,7 @@
 #include "k_proj.h"
 #include "k_marg.h"
 #include "k_lapl.h"
+#include "k_tree_loss.h"
 #include "k_gemm.h"
 #include "k_gemm_ring.h"
 #include "k_generic.h"
@@ -1887,6 +1888,70 @@ int ggnn_tree_marginals(const ggnn_dims* d, const float* probs_head, int32_t o, 
                      need ? (float*)workspace : nullptr, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
   LAUNCHCHK();
   return GGNN_OK;
+}
+
+// the tree-structured training loss (k_tree_loss.h around the family's marginal
+// kernel); booked under the heads kind.  The workspace: n_eff int32 [b], then
+// the marginal kernel's own.
+static size_t tree_loss_head_bytes(int32_t b) { return ((size_t)b * 4 + 255) & ~(size_t)255; }
+size_t ggnn_tree_loss_workspace_bytes(int32_t b, int32_t v, int32_t family) {
+  if (b < 1) return 0;
+  return tree_loss_head_bytes(b) + (family == 1 ? ggnn_projective_marginals_workspace_bytes(b, v)
+                                                : ggnn_tree_marginals_workspace_bytes(b, v));
+}
+static int tree_loss_impl(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                          const int32_t* n_nodes, int32_t family, int32_t single_root, float target_num,
+                          const float* tn_dev, float* marg, float* logz, int32_t* status, int32_t* used,
+                          float* loss_inout, void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  const char* const name = "tree_loss";
+  const bool null_arg =
+      !probs_head || !gold_head || !n_nodes || !marg || !logz || !status || !used || !loss_inout || !workspace;
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
+  if (family != 0 && family != 1) return fail(GGNN_EINVAL, "tree_loss: family must be 0 (all trees) or 1 (projective)");
+  if (!tn_dev && !(target_num > 0.f)) return fail(GGNN_EINVAL, "tree_loss: target_num must be > 0");
+  if (marg == probs_head) return fail(GGNN_EINVAL, "tree_loss: marg must not alias probs_head");
+  const size_t need = ggnn_tree_loss_workspace_bytes(d->b, d->v, family);
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int* n_eff = (int*)workspace;
+  const size_t head = tree_loss_head_bytes(d->b);
+  {
+    Prof p(K_HEADS, s);
+#define TLG(NI_)                                                                                                   \
+  hipLaunchKernelGGL(k_tree_loss_gold<NI_>, dim3((unsigned)d->b), dim3(256), 0, s, gold_head, probs_head, (int)o, \
+                     (const int*)n_nodes, (int)d->v, (int)family, (int)single_root, n_eff)
+    if (o <= 256) TLG(4);
+    else TLG(HEAD_MAXO / 64);
+#undef TLG
+    LAUNCHCHK();
+  }
+  // the family's marginals over the eligible graphs (n_eff = 0: marg = probs, status 0)
+  void* inner = need > head ? (void*)((char*)workspace + head) : nullptr;
+  if (int rc = (family == 1 ? ggnn_projective_marginals : ggnn_tree_marginals)(
+          d, probs_head, o, n_eff, single_root, marg, logz, nullptr, status, inner, need - head, stream))
+    return rc;
+  {
+    Prof p(K_HEADS, s);
+    hipLaunchKernelGGL(k_tree_loss_fold, dim3(1), dim3(64), 0, s, (const int*)status, (const float*)logz, (int)d->b,
+                       target_num, tn_dev, (int*)used, loss_inout);
+    LAUNCHCHK();
+  }
+  return GGNN_OK;
+}
+int ggnn_tree_loss(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                   const int32_t* n_nodes, int32_t family, int32_t single_root, float target_num, float* marg,
+                   float* logz, int32_t* status, int32_t* used, float* loss_inout, void* workspace,
+                   size_t workspace_bytes, ggnn_stream_t stream) {
+  return tree_loss_impl(d, probs_head, o, gold_head, n_nodes, family, single_root, target_num, nullptr, marg, logz,
+                        status, used, loss_inout, workspace, workspace_bytes, stream);
+}
+int ggnn_tree_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                       const int32_t* n_nodes, int32_t family, int32_t single_root, const float* target_num,
+                       float* marg, float* logz, int32_t* status, int32_t* used, float* loss_inout, void* workspace,
+                       size_t workspace_bytes, ggnn_stream_t stream) {
+  if (!target_num) return fail(GGNN_EINVAL, "tree_loss_dev: NULL target_num");
+  return tree_loss_impl(d, probs_head, o, gold_head, n_nodes, family, single_root, 0.f, target_num, marg, logz, status,
+                        used, loss_inout, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -963,3 +963,87 @@ def tree_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.float6
         scores[g, :n, :n] = np.where(ok, np.rint(marg[g, :n, :n].astype(np.float32) * np.float32(MARG_SCORE_SCALE)),
                                      TREE_FORBIDDEN).astype(np.int32)
     return marg, logz, scores, status, cond
+
+
+# ------------------------------------------------ tree-structured training loss
+# Host form of ``ggnn_tree_loss`` (include/ggnn.h, csrc/k_tree_loss.h): the
+# negative log-likelihood of the gold tree under the distribution over trees
+# that the head probabilities define (Koo et al. 2007).  Per graph, with p the
+# softmax of the head logits z and y the gold heads,
+#   L = -sum_d ln p[d][gold_d] + ln Z,    dL/dz[d][k] = marg[d][k] - y[d][k]
+# (every word's marginals sum to 1 over its allowed arcs, so the -p[d][k] of the
+# first term and the +p[d][k] that ln Z's chain rule leaves cancel).  The first
+# term is the heads' cross-entropy; these functions give the second.
+TREE_LOSS_FAMILIES = {"nonprojective": 0, "projective": 1}
+
+
+def _tree_loss_family(family):
+    f = TREE_LOSS_FAMILIES.get(family, family)
+    if isinstance(f, (bool, str)) or f not in (0, 1):
+        raise ValueError("family must be 0 / 'nonprojective' or 1 / 'projective', got %r" % (family,))
+    return int(f)
+
+
+def gold_tree_ok(gold_head, probs_head, n_nodes, family, single_root=True):
+    """bool [b]: whether a graph's gold heads have a probability under the
+    distribution of ``family`` (the eligibility rule of ggnn_tree_loss).
+    gold_head, probs_head: float32 [b, v, o]; n_nodes [b], clipped as the
+    kernels clip it.  True when n >= 2 and: every row 1..n-1 of gold_head holds
+    exactly one 1.0 and zeros otherwise; that column is an allowed arc (< n,
+    not the word itself, its potential finite and > 0); row 0 and the rows >= n
+    are all zero; the heads reach node 0 from every word; with single_root
+    exactly one word takes column 0; with the projective family no two arcs
+    cross (ROOT leftmost)."""
+    family = _tree_loss_family(family)
+    y = np.asarray(gold_head, np.float32)
+    p = np.asarray(probs_head, np.float32)
+    if y.ndim != 3 or y.shape != p.shape:
+        raise ValueError("gold_head and probs_head must be [b, v, o] alike")
+    b, v, o = y.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("the tree loss needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    nn = _node_counts(n_nodes, b, v, o)
+    ok = np.zeros(b, bool)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2:
+            continue
+        ones = y[g] == 1
+        if not ((ones | (y[g] == 0)).all() and not ones[0].any() and not ones[n:].any()
+                and (ones[1:n].sum(axis=1) == 1).all()):
+            continue
+        heads = np.concatenate([[0], ones[1:n].argmax(axis=1)])
+        w = np.arange(1, n)
+        if (heads[1:] >= n).any() or (heads[1:] == w).any():
+            continue
+        pot = p[g, w, heads[1:]]
+        if not (np.isfinite(pot) & (pot > 0)).all():
+            continue
+        if not is_tree(heads, n, bool(single_root)):
+            continue
+        if family == 1 and not is_projective(heads, n):
+            continue
+        ok[g] = True
+    return ok
+
+
+def tree_loss_arrays(probs_head, gold_head, n_nodes, family, single_root, target_num, dtype=np.float64):
+    """The host form of ``ggnn_tree_loss``: returns (loss_term, marg [b, v, o],
+    logz [b], status int32 [b], used int32 [b]).  The graphs that gold_tree_ok
+    admits keep their node count, the others get n = 0; the family's
+    *_marginals_arrays runs on those counts (so a graph that is not admitted
+    has status 0 and marg = a copy of probs_head: the plain cross-entropy and
+    its gradient); used = (status == 1) and loss_term = (sum over the used
+    graphs of logz) / target_num, what the call adds to head 0's loss.  marg -
+    gold_head on a used graph is the gradient of that graph's loss with respect
+    to the head logits, times target_num.  Tables / matrices in ``dtype``."""
+    family = _tree_loss_family(family)
+    p = np.asarray(probs_head, np.float32)
+    b, v, o = p.shape
+    ok = gold_tree_ok(gold_head, p, n_nodes, family, single_root)
+    n_eff = np.where(ok, _node_counts(n_nodes, b, v, o), 0)
+    run = projective_marginals_arrays if family == 1 else tree_marginals_arrays
+    marg, logz, _, status, _ = run(p, n_eff, single_root, dtype)
+    used = (status == 1).astype(np.int32)
+    term = float(np.sum(logz[used == 1].astype(np.float64))) / float(target_num)
+    return term, marg, logz, status, used

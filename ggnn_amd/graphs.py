@@ -10,8 +10,8 @@ shapes never pay for a capture); its second batch is captured and replayed.
 
 What stays fixed across replays of one graph (its key: batch shape (b, v),
 the word_inputs width, the dropout keep probabilities, train / eval, the task,
-whether Adam is in the graph and then grad_scale, the word table's layout, and
-the host scalars below): every device pointer (the step owns its engine --
+whether Adam is in the graph and then grad_scale, the word table's layout,
+params['structured_loss'] with its root mode, and the host scalars below): every device pointer (the step owns its engine --
 adjacency, workspaces -- and its heads workspace; the variables, their Adam
 slots and the flat gradient buffer belong to the model), every launch shape
 and every host scalar the library bakes into a launch.  Of those scalars the
@@ -27,7 +27,8 @@ SMALL_NUMBER.  make_optimizer replaces the Adam slots, so it drops every
 captured step.  What changes per batch lives in one device buffer
 (``StepInputs``) that the graph reads: word_inputs, the edge list and graph
 offsets (capacity b*v rows; the kernels read only rows [off[0], off[b])), both
-heads' labels, and the step scalars -- the three dropout seeds
+heads' labels, the graphs' node counts (params['structured_loss']), and the
+step scalars -- the three dropout seeds
 (GGNN_SEED_DEVICE), the loss normaliser target_num (ggnn_heads_*_dev) and the
 Adam step count (ggnn_adam_step_dev).  Results equal the eager step's on the
 same inputs and seeds (tests/test_gpu_graphs.py).
@@ -69,14 +70,17 @@ class StepLayout:
         off = _al(off + n * self.o * 4)
         self.ye = off
         off = _al(off + n * self.oe * 4)
+        self.n_nodes = off      # int32 [b]: the graphs' node counts (the structured loss)
+        off = _al(off + self.b * 4)
         self.nbytes = off
 
     @property
     def edge_capacity(self) -> int:
         return self.b * self.v
 
-    def fill(self, host: np.ndarray, seeds, step: int, target_num, wi, edges, offs, yh, ye) -> None:
-        """Write one batch into ``host`` (a uint8 array of >= nbytes)."""
+    def fill(self, host: np.ndarray, seeds, step: int, target_num, wi, edges, offs, yh, ye, n_nodes=None) -> None:
+        """Write one batch into ``host`` (a uint8 array of >= nbytes).
+        n_nodes: the graphs' node counts [b], or None: zeros."""
         b, v = self.b, self.v
         host[0:24].view(np.uint64)[:] = np.asarray(seeds, dtype=np.uint64)
         host[24:32].view(np.int64)[0] = int(step)
@@ -87,6 +91,7 @@ class StepLayout:
         host[self.offs:self.offs + (b + 1) * 4].view(np.int32)[:] = offs
         host[self.yh:self.yh + b * v * self.o * 4].view(np.float32)[:] = yh.reshape(-1)
         host[self.ye:self.ye + b * v * self.oe * 4].view(np.float32)[:] = ye.reshape(-1)
+        host[self.n_nodes:self.n_nodes + b * 4].view(np.int32)[:] = 0 if n_nodes is None else np.asarray(n_nodes)
 
 
 class StepInputs:
@@ -105,6 +110,7 @@ class StepInputs:
         self.offs = u[L.offs:L.offs + (b + 1) * 4].view(torch.int32)
         self.yh = u[L.yh:L.yh + n * L.o * 4].view(torch.float32).view(b, v, L.o)
         self.ye = u[L.ye:L.ye + n * L.oe * 4].view(torch.float32).view(b, v, L.oe)
+        self.n_nodes = u[L.n_nodes:L.n_nodes + b * 4].view(torch.int32)
 
     def seed_address(self, i: int) -> int:
         return self.seeds.data_ptr() + 8 * int(i)

@@ -5,7 +5,9 @@
   columns, embedding dropout, concat, zero pad to ``hidden_size``.
 * ``OutputHeads`` -- ``gated_regression`` for ``--pr btb``
   (chem_tensorflow_dense.py:439-516) with ``MLP(2h, o, [], keep)``
-  (utils.py:40-84) and the btb cross-entropy (chem_tensorflow.py:349-403).
+  (utils.py:40-84) and the btb cross-entropy (chem_tensorflow.py:349-403);
+  not in the reference: ``tree_loss=`` turns head 0's loss into the negative
+  log-likelihood of the gold tree (``ggnn_tree_loss``, ``csrc/k_tree_loss.h``).
 
 Both run in libggnn.so (``ggnn_embed_*``, ``ggnn_heads_*``; kernels in
 ``csrc/k_head.h``); torch tensors only hold device memory.  The autograd
@@ -176,7 +178,12 @@ class OutputHeads:
         self._proj_ws = None   # ggnn_projective_decode's workspace (graphs above PROJ_LDS_MAXN nodes)
         self._marg_ws = None   # ggnn_projective_marginals' workspace (graphs above MARG_LDS_MAXN nodes)
         self._lapl_ws = None   # ggnn_tree_marginals' workspace (graphs above LAPL_LDS_MAXN nodes)
+        self._loss_ws = None   # ggnn_tree_loss' workspace (n_eff, then the family's marginals workspace)
         self._saved = None
+        # the last forward's structured loss (tree_loss=): the marginals that
+        # stand in head 0's probs place in the backward, and used int32 [b];
+        # None after a forward without it
+        self.tree_marg = self.tree_used = None
 
     def _table(self, heads, labels, probs, dws=None, dbs=None):
         arr = (OutputHead * len(heads))()
@@ -188,12 +195,20 @@ class OutputHeads:
         return arr
 
     def forward(self, hT, h0, heads, labels=None, keep=1.0, seed=0, target_num=1.0, loss_out=None, probs_out=None,
-                seed_device=False):
+                seed_device=False, tree_loss=None):
         """Returns (probs list [b, v, o], loss tensor [nheads] or None).
         loss_out / probs_out: optional output buffers (loss [nheads] fp32).
         target_num: a number, or a device fp32 tensor of one element
         (ggnn_heads_forward_dev); seed_device: seed is the address of a
-        device uint64 (GGNN_SEED_DEVICE)."""
+        device uint64 (GGNN_SEED_DEVICE).  tree_loss: None, or (family,
+        single_root, n_nodes int32 [b] on the device): head 0's loss becomes
+        the tree-structured one (``tree_loss`` below, after the heads' forward
+        on the same stream: ln Z / target_num is added into loss[0]); the
+        marginals and used [b] stay on the object (tree_marg, tree_used) and
+        the next ``backward`` takes the marginals in head 0's probs place.
+        The returned probs are the softmax either way."""
+        if tree_loss is not None and labels is None:
+            raise ValueError("tree_loss needs labels")
         b, v, h = hT.shape
         dev = hT.device
         probs = probs_out if probs_out is not None else [torch.empty(b, v, W.shape[1], dtype=torch.float32, device=dev)
@@ -220,16 +235,66 @@ class OutputHeads:
                                                     float(target_num), _ptr(loss), _ptr(self._ws), _stream()),
                        "ggnn_heads_forward")
         self._saved = (b, v, h)
+        self.tree_marg = self.tree_used = None
+        if tree_loss is not None:
+            family, single_root, n_nodes = tree_loss
+            self.tree_marg, _, _, self.tree_used = self.tree_loss(probs[0], labels[0], n_nodes, family, single_root,
+                                                                  target_num, loss)
         return probs, loss
+
+    def tree_loss(self, probs_head, gold_head, n_nodes, family, single_root, target_num, loss, workspace=None):
+        """The tree-structured loss term on the current stream (ggnn_tree_loss,
+        include/ggnn.h): ``loss[0] += (sum over the used graphs of ln Z) /
+        target_num``.  probs_head, gold_head: float32 [b, v, o]; n_nodes: int32
+        [b]; family: 0 / "nonprojective" (all dependency trees) or 1 /
+        "projective"; target_num: a number or a device fp32 tensor of one
+        element; loss: a device fp32 tensor, element 0 added to.  Returns
+        (marg float32 [b, v, o], logz float32 [b], status int32 [b], used
+        int32 [b]): a used graph's marg holds the arc marginals (what the
+        heads' backward takes in the probabilities' place), any other graph's
+        a copy of probs_head.  workspace: a uint8 tensor to use instead of the
+        binding's own."""
+        _check_tensor(probs_head, "probs_head", torch.float32)
+        family = {"nonprojective": 0, "projective": 1}.get(family, family)
+        if family not in (0, 1):
+            raise ValueError("family must be 0 / 'nonprojective' or 1 / 'projective'")
+        b, v, o = probs_head.shape
+        dev = probs_head.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("tree_loss needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
+        _check_tensor(gold_head, "gold_head", torch.float32)
+        if gold_head.shape != probs_head.shape or gold_head.device != dev:
+            raise ValueError("gold_head must have probs_head's shape and device")
+        _check_n_nodes(n_nodes, b, dev)
+        if loss.dtype != torch.float32 or loss.device != dev or loss.numel() < 1 or not loss.is_contiguous():
+            raise ValueError("loss must be a contiguous float32 tensor on %s" % dev)
+        need = int(self._lib.ggnn_tree_loss_workspace_bytes(b, v, family))
+        workspace = self._workspace("_loss_ws", need, dev, workspace)
+        marg = torch.empty_like(probs_head)
+        logz = torch.empty(b, dtype=torch.float32, device=dev)
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        used = torch.empty(b, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        on_dev = isinstance(target_num, torch.Tensor)
+        fn = self._lib.ggnn_tree_loss_dev if on_dev else self._lib.ggnn_tree_loss
+        _lib.check(fn(ctypes.byref(d), _ptr(probs_head), o, _ptr(gold_head), _ptr(n_nodes), int(family),
+                      int(bool(single_root)), _ptr(target_num) if on_dev else float(target_num), _ptr(marg),
+                      _ptr(logz), _ptr(status), _ptr(used), _ptr(loss), _ptr(workspace), workspace.numel(), _stream()),
+                   "ggnn_tree_loss_dev" if on_dev else "ggnn_tree_loss")
+        return marg, logz, status, used
 
     def backward(self, hT, h0, heads, labels, probs, target_num=1.0, d_loss=None, dws=None, dbs=None, dhT=None,
                  dh0=None):
         """Gradients of sum(loss) (times d_loss, a device scalar): dW, db per
         head and (dhT, dh0).  Uses the workspace of the last forward.  dws, dbs,
-        dhT, dh0: optional output buffers (overwritten)."""
+        dhT, dh0: optional output buffers (overwritten).  After a forward with
+        tree_loss the marginals it kept stand in probs[0]'s place (dZ = marg -
+        y on the used graphs); the caller's probs are not written."""
         b, v, h = hT.shape
         if self._saved != (b, v, h):
             raise RuntimeError("heads backward without a matching forward")
+        if self.tree_marg is not None:
+            probs = [self.tree_marg] + list(probs[1:])
         dws = dws if dws is not None else [torch.empty_like(W) for W, _ in heads]
         dbs = dbs if dbs is not None else [torch.empty_like(bb) for _, bb in heads]
         dhT = dhT if dhT is not None else torch.empty_like(hT)
@@ -485,16 +550,18 @@ class EmbedFunction(torch.autograd.Function):
 
 
 class HeadsFunction(torch.autograd.Function):
-    """loss = sum over heads of the btb cross-entropy; also returns the probs
+    """loss = sum over heads of the btb cross-entropy (tree_loss, OutputHeads.
+    forward's: head 0's is the tree-structured loss); also returns the probs
     (computed_values)."""
 
     @staticmethod
-    def forward(ctx, oh, labels, keep, seed, target_num, hT, h0, *wb):
+    def forward(ctx, oh, labels, keep, seed, target_num, tree_loss, hT, h0, *wb):
         heads = [(wb[2 * i], wb[2 * i + 1]) for i in range(len(wb) // 2)]
-        probs, loss = oh.forward(hT, h0, heads, labels, keep, seed, target_num)
+        probs, loss = oh.forward(hT, h0, heads, labels, keep, seed, target_num, tree_loss=tree_loss)
         ctx.oh, ctx.labels, ctx.target_num = oh, labels, target_num
         ctx.save_for_backward(hT, h0, *wb)
         ctx.probs = probs
+        ctx.marg = oh.tree_marg
         ctx.mark_non_differentiable(*probs)
         return (loss.sum(),) + tuple(probs)
 
@@ -502,9 +569,11 @@ class HeadsFunction(torch.autograd.Function):
     def backward(ctx, d_loss, *unused):
         hT, h0, *wb = ctx.saved_tensors
         heads = [(wb[2 * i], wb[2 * i + 1]) for i in range(len(wb) // 2)]
+        if ctx.oh.tree_marg is not ctx.marg:
+            raise RuntimeError("the heads ran another forward since this loss was produced")
         dws, dbs, dhT, dh0 = ctx.oh.backward(hT, h0, heads, ctx.labels, ctx.probs, ctx.target_num,
                                              d_loss.reshape(1).contiguous())
         grads = []
         for dw, db in zip(dws, dbs):
             grads += [dw, db]
-        return (None, None, None, None, None, dhT, dh0) + tuple(grads)
+        return (None, None, None, None, None, None, dhT, dh0) + tuple(grads)

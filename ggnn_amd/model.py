@@ -29,6 +29,10 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
   batch / of raw sentences), ``score_epoch`` and ``evaluate_batch(on_device=
   True)`` (the scores from per-graph counts): ``decoding.DecodingMixin``, the
   decode and the tree passes after it on the device (``tree=``, ``confidence=``)
+* not in the reference: ``params['structured_loss']`` ("nonprojective" /
+  "projective"): the head's loss as the negative log-likelihood of the gold
+  tree (``ggnn_tree_loss`` after the heads' forward, in every step body;
+  ``ops['tree_loss_used']``: the graphs of the last step it applied to)
 
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
@@ -90,11 +94,12 @@ class _StepFeed:
     the batch's adjacency."""
 
     def __init__(self, wi, seeds, seed_values, seed_device, labels, target_num, engine, heads, stage, b, v,
-                 target_num_value=None):
+                 target_num_value=None, n_nodes=None):
         self.wi, self.seeds, self.seed_values, self.seed_device = wi, seeds, seed_values, seed_device
         self.labels, self.target_num, self.engine, self.heads, self.stage = labels, target_num, engine, heads, stage
         self.b, self.v = b, v
         self.target_num_value = target_num if target_num_value is None else target_num_value
+        self.n_nodes = n_nodes    # int32 [b] on the device (params['structured_loss']), else None
 
 
 class _Propagate(torch.autograd.Function):
@@ -146,6 +151,12 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         self.params = self.default_params()
         if params:
             self.params.update(params)
+        if self.params.get("structured_loss") not in (None,) + tuple(_eval.TREE_LOSS_FAMILIES):
+            raise ValueError("params['structured_loss'] must be None, 'nonprojective' or 'projective', got %r"
+                             % (self.params["structured_loss"],))
+        if self.params.get("structured_loss_single_root", True) not in (True, False):
+            raise ValueError("params['structured_loss_single_root'] must be True or False, got %r"
+                             % (self.params["structured_loss_single_root"],))
         if num_edge_types is None:
             raise ValueError("num_edge_types is required (len(dep_list)+1 in the reference, "
                              "chem_tensorflow.py:198)")
@@ -193,6 +204,10 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
             "compact_adjacency": False,   # not in the reference: edge-list feed (ggnn_set_adjacency_edges)
             "hip_graphs": True,           # not in the reference: captured steps for edge-list feeds (graphs.py)
             "hip_graph_cache_mb": 16384,  # not in the reference: device memory the captured steps may hold
+            # not in the reference: the head's loss as the negative log-likelihood of the gold TREE
+            # (None: the per-word cross-entropy; "nonprojective" / "projective": ggnn_tree_loss)
+            "structured_loss": None,
+            "structured_loss_single_root": True,
         }
 
     @property
@@ -240,7 +255,8 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         self._heads = None
         self._decoder = None
         self._up_nodes = Uploader()
-        self._last_labels = None   # the last forward's labels on the device: the decode's gold inputs
+        self._up_loss_nodes = Uploader()   # the structured loss's node counts (the eager paths)
+        self._last_labels = None  # the last forward's labels on the device: the decode's gold inputs
         # the last forward's dropout draws, by stage (keep probabilities, seed, ...)
         self.last_embed = self.last_dropout = self.last_heads = None
         # the epoch loops' device -> host fetches: run_epoch's (loss, both
@@ -430,8 +446,12 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         keep = self._out_keep()
         seed = self._seed()
         (gw, gb), (gew, geb) = self._heads_list(task_id)
-        loss, probs, probs_e = HeadsFunction.apply(self._output_heads(), labels, keep, seed, target_num, hT, h0,
+        n = self._loss_n_nodes(self.placeholders)
+        tree_loss = self._tree_loss_arg(None if n is None else self._up_loss_nodes(n, self.device))
+        oh = self._output_heads()
+        loss, probs, probs_e = HeadsFunction.apply(oh, labels, keep, seed, target_num, tree_loss, hT, h0,
                                                    gw, gb, gew, geb)
+        self.ops["tree_loss_used"] = oh.tree_used
         self.ops["loss"] = loss
         self.ops["computed_values"] = probs.reshape(b, v * o)
         self.ops["computed_values_edges"] = probs_e.reshape(b, v * oe)
@@ -455,6 +475,27 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         """sum(target_mask[task]) of the staged batch (chem_tensorflow.py:358-360)."""
         tmask = np.asarray(self.placeholders["target_mask"], np.float64)
         return float(tmask[self.params["task_ids"].index(task_id)].sum())
+
+    def _structured(self):
+        """params['structured_loss'] as (family, single_root) of ggnn_tree_loss, or None (off)."""
+        kind = self.params.get("structured_loss")
+        if kind is None:
+            return None
+        return _eval.TREE_LOSS_FAMILIES[kind], bool(self.params.get("structured_loss_single_root", True))
+
+    def _loss_n_nodes(self, ph):
+        """The node counts the structured loss runs on: _feed_n_nodes, and 0 for
+        every graph of a feed whose masks are not in closed form (the local
+        loss for that batch); None with params['structured_loss'] off."""
+        if self._structured() is None:
+            return None
+        n = self._feed_n_nodes(ph)
+        return np.zeros(int(ph["num_graphs"]), np.int32) if n is None else n.astype(np.int32)
+
+    def _tree_loss_arg(self, n_nodes):
+        """OutputHeads.forward's tree_loss= for device node counts (None: off)."""
+        st = self._structured()
+        return None if st is None or n_nodes is None else st + (n_nodes,)
 
     def _out_keep(self) -> float:
         return float(self.placeholders.get("out_layer_dropout_keep_prob", self.params["out_layer_dropout_keep_prob"]))
@@ -642,8 +683,9 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         # in the graph; a change captures a fresh step, the old one ages out)
         opt = self.optimizer
         baked = (int(self.params["num_timesteps"]),) + ((opt.lr, opt.b1, opt.b2, opt.eps, opt.clip) if adam else ())
+        # (the structured loss's family and root mode are launch arguments too)
         key = (bool(training), adam, b, v, wi.shape[-1], keeps, task_id, float(grad_scale) if adam else 1.0, sparse,
-               baked)
+               baked, self._structured())
         cs = self._graphs.get(key)
         if cs is None:
             cs = self._graphs[key] = CapturedStep(StepLayout(b, v, wi.shape[-1], o, oe), self._new_engine(),
@@ -658,7 +700,8 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         L = cs.layout
         i, host = self._ring.acquire(L.nbytes)
         L.fill(host.numpy(), seeds, step, target_num, wi.astype(np.int32), edges, offs,
-               np.asarray(ph["target_values_head"], np.float32), np.asarray(ph["target_values_edges"], np.float32))
+               np.asarray(ph["target_values_head"], np.float32), np.asarray(ph["target_values_edges"], np.float32),
+               n_nodes=self._loss_n_nodes(ph))
         stream = torch.cuda.current_stream(self.device)
         cs.inputs.buf[:L.nbytes].copy_(host, non_blocking=True)
         self._ring.release(i, stream)
@@ -666,7 +709,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         sf = _StepFeed(inp.wi, tuple(inp.seed_address(k) for k in range(3)), tuple(seeds), True, [inp.yh, inp.ye],
                        inp.target_num, cs.engine, cs.heads,
                        lambda eng: eng.set_adjacency_edges((inp.edges, inp.offs), v, self.num_edge_types), b, v,
-                       target_num_value=target_num)
+                       target_num_value=target_num, n_nodes=inp.n_nodes)
 
         def body():
             if training:
@@ -679,7 +722,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
             else:
                 _, _, probs, loss = self._forward(sf, task_id, training=False)
                 loss = loss.sum()
-            return {"loss": loss, "probs": probs}
+            return {"loss": loss, "probs": probs, "used": cs.heads.tree_used}
 
         if cs.graph is None and cs.runs == 0:
             # a shape's first batch runs eagerly (on the same device inputs):
@@ -712,6 +755,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         probs = out["probs"]
         self.ops["computed_values"] = probs[0].reshape(b, v * o)
         self.ops["computed_values_edges"] = probs[1].reshape(b, v * oe)
+        self.ops["tree_loss_used"] = out["used"]
         self._last_labels = [inp.yh, inp.ye]
         loss = out["loss"]
         if training and not adam:
@@ -763,7 +807,9 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         self.last_dropout = dict(edge_keep=edge_keep, state_keep=state_keep, seed=sf.seed_values[1])
         keep_o = self._out_keep()
         probs, loss = sf.heads.forward(hT, h0, self._heads_list(task_id), sf.labels, keep_o, sf.seeds[2],
-                                       sf.target_num, loss_out=loss_out, seed_device=sf.seed_device)
+                                       sf.target_num, loss_out=loss_out, seed_device=sf.seed_device,
+                                       tree_loss=self._tree_loss_arg(sf.n_nodes))
+        self.ops["tree_loss_used"] = sf.heads.tree_used
         self.last_heads = dict(keep=keep_o, seed=sf.seed_values[2], target_num=sf.target_num_value)
         return h0, hT, probs, loss
 
@@ -792,8 +838,10 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         b, v = int(self.placeholders["num_graphs"]), int(self.placeholders["num_vertices"])
         labels = self._head_labels(b, v)
         count = self._target_count(task_id) if target_count is None else target_count
+        n = self._loss_n_nodes(self.placeholders)
         return _StepFeed(wi, seeds, seeds, False, labels, float(count + SMALL_NUMBER), self._engine("main"),
-                         self._output_heads(), self._stage_adjacency, b, v)
+                         self._output_heads(), self._stage_adjacency, b, v,
+                         n_nodes=None if n is None else self._up_loss_nodes(n, self.device))
 
     def _check_front_end_width(self):
         width = self.loc_embedding_size * 2 + self.pos_embedding_size + self.word_embedding_size

@@ -614,6 +614,64 @@ int ggnn_tree_marginals(const ggnn_dims* d,        /* b, v used */
                         int32_t* status,           /* device [b] out */
                         void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* The tree-structured training loss (Koo et al. 2007): the negative
+ * log-likelihood of the gold tree under the distribution that
+ * ggnn_tree_marginals (family 0: all dependency trees) or
+ * ggnn_projective_marginals (family 1: projective trees) define.  For one graph
+ *   L = -sum_d ln p[d][gold_d] + ln Z,   dL/dz[d][k] = marg[d][k] - y[d][k]
+ * (z the head logits, p their softmax, y = gold_head).  The first term is the
+ * cross-entropy ggnn_heads_forward has already put into the loss; this call,
+ * after it on the same stream, adds the second and leaves in marg what
+ * ggnn_heads_backward takes in head 0's `probs` place (its dZ = g * (probs *
+ * sum(y) - y) is then g * (marg - y) on every row with one gold head and 0 on
+ * row 0 and the padding rows).
+ * A graph is ELIGIBLE when, with n = n_nodes[g] clamped as in ggnn_tree_decode,
+ * n >= 2 and
+ *   every row 1..n-1 of gold_head[g] holds exactly one 1.0f and zeros otherwise,
+ *   that column is an allowed arc of the marginals (< n, not the word itself,
+ *   its potential finite and > 0),
+ *   row 0 and the rows >= n are all zero,
+ *   following the heads from any word reaches node 0,
+ *   with single_root exactly one word takes column 0, and
+ *   with family 1 no two arcs cross (ROOT leftmost),
+ * i.e. when the gold tree has a probability under the distribution.  Three
+ * launches: the eligibility kernel writes n_eff[g] = n or 0 into the workspace;
+ * the family's marginal kernel runs unchanged on n_eff (scores = NULL) and
+ * writes marg, logz and status by its own contract, so that a graph that is
+ * not eligible (status 0) or has no finite ln Z (status 2) keeps marg[g] = a
+ * byte copy of probs_head[g], i.e. the plain cross-entropy and its gradient;
+ * the last sets used[g] = (status[g] == 1) and
+ *   loss_inout[0] += (sum over the used graphs of logz[g]) / target_num,
+ * the sum taken in double in a fixed order.  target_num: as ggnn_heads_forward
+ * (the _dev form reads a device float > 0; the two give the same bits).
+ * ggnn_tree_loss_workspace_bytes(b, v, family) = b int32 rounded up to 256
+ * bytes + the family's marginals workspace (0 up to GGNN_LAPL_LDS_MAXN /
+ * GGNN_MARG_LDS_MAXN nodes); a smaller workspace is rejected.  Needs v <= o,
+ * v <= GGNN_TREE_MAXV, o <= 1024; marg must not alias probs_head.  No atomics,
+ * every loop bounded by a function of n.  Stream-ordered, allocation-free,
+ * legal under stream capture, bit-reproducible; booked under the heads kernel
+ * kind. */
+size_t ggnn_tree_loss_workspace_bytes(int32_t b, int32_t v, int32_t family);
+int ggnn_tree_loss(const ggnn_dims* d,        /* b, v used */
+                   const float* probs_head,   /* device [b][v][o] */
+                   int32_t o,
+                   const float* gold_head,    /* device [b][v][o] */
+                   const int32_t* n_nodes,    /* device [b] */
+                   int32_t family,            /* 0 all dependency trees, 1 projective */
+                   int32_t single_root,       /* 0 / 1 */
+                   float target_num,
+                   float* marg,               /* device [b][v][o] out */
+                   float* logz,               /* device [b] out */
+                   int32_t* status,           /* device [b] out */
+                   int32_t* used,             /* device [b] out */
+                   float* loss_inout,         /* device float, added to */
+                   void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+int ggnn_tree_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                       const int32_t* n_nodes, int32_t family, int32_t single_root,
+                       const float* target_num, /* device float */
+                       float* marg, float* logz, int32_t* status, int32_t* used, float* loss_inout,
+                       void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */

@@ -9,6 +9,16 @@ step time and the HIP-event kernel breakdown.
 Variants: skip (channel skipping, the default engine), dense
 (skip_empty_channels=False), keepXX (training dropout at keep 0.XX), ekXX /
 stXX (edge-weight / state dropout alone at keep 0.XX).
+
+--structured-loss {nonprojective,projective}: every variant runs three times
+per round: as it is, (name + "+marginals") with the family's marginal kernel
+alone after the backward (the yardstick) and (name + "+tree_loss") with
+ggnn_tree_loss there, on fixed head probabilities [b, v, 150] (the softmax of
+N(0, 2^2) logits) and the graphs' own heads as gold (--trees; a chain
+otherwise; multi-root, the random trees have several ROOT children;
+projective: a random projective tree of the graph's size, the random trees
+cross): what params['structured_loss'] adds to a step, all three alternating
+in one process.  A first line says how many graphs the loss used.
 """
 import argparse
 import json
@@ -32,11 +42,15 @@ def main():
     ap.add_argument("--reference", action="store_true",
                     help="with --trees: the reference's model (hidden 400, T = 4), edge lists staged once, pair mode")
     ap.add_argument("--batch", type=int, default=256, help="graphs per batch (20: run_epoch's batch_size)")
+    ap.add_argument("--structured-loss", choices=("nonprojective", "projective"), default=None,
+                    help="also time every variant with ggnn_tree_loss of this family in the step")
     args = ap.parse_args()
     import torch
     from ggnn_amd import _lib
     from ggnn_amd.dist import GRAD_ORDER, FlatGradients
     from ggnn_amd.engine import PropagationEngine
+    from ggnn_amd.evaluation import random_projective_heads
+    from ggnn_amd.heads import OutputHeads
     from ggnn_amd.optim import ClipAdam
     import ggnn_oracle as O
 
@@ -67,7 +81,28 @@ def main():
     dhT = torch.from_numpy(np.random.default_rng(7).standard_normal((b, v, h)).astype(np.float32)).to(dev)
     opt = ClipAdam([w_d[k] for k in GRAD_ORDER], learning_rate=0.003)
 
-    def make(variant):
+    tl = None
+    if args.structured_loss:
+        # the heads' side of the step: fixed probabilities, the graphs' heads as gold
+        o = 150
+        rng_h = np.random.default_rng(29)
+        z = rng_h.normal(0.0, 2.0, (b, v, o))
+        p = np.exp(z - z.max(axis=2, keepdims=True))
+        p = (p / p.sum(axis=2, keepdims=True)).astype(np.float32)
+        y = np.zeros((b, v, o), np.float32)
+        nn = np.full(b, v, np.int32)
+        for g in range(b):
+            ed = graphs[g] if graphs is not None else [(i - 1, 1, i) for i in range(1, v)]
+            nn[g] = len(ed) + 1
+            if args.structured_loss == "projective":    # (the random trees cross: a random projective tree instead)
+                ed = [(hd, 1, i) for i, hd in enumerate(random_projective_heads(nn[g], rng_h)) if i]
+            for src, _, dst in ed:
+                y[g, dst, src] = 1.0
+        oh = OutputHeads(h)
+        tl = dict(oh=oh, p=torch.from_numpy(p).to(dev), y=torch.from_numpy(y).to(dev),
+                  n=torch.from_numpy(nn).to(dev), loss=torch.zeros(2, device=dev), tn=float(nn.sum() - b))
+
+    def make(variant, extra=None):
         keep = 1.0
         ekeep = skeep = None     # edge / state keep when they differ (variants ekXX, stXX)
         kw = {}
@@ -98,9 +133,23 @@ def main():
             eng.forward(h0_d, pack, T, training=True, out=out, state_keep=sk)
             eng.backward(dhT, gv)
             opt.step([grads.views[k] for k in GRAD_ORDER])
+            if extra == "tree_loss":
+                tl["oh"].tree_loss(tl["p"], tl["y"], tl["n"], args.structured_loss, False, tl["tn"], tl["loss"])
+            elif extra == "marginals":      # the family's marginal kernel alone: the yardstick of the two new launches
+                run = tl["oh"].projective_marginals if args.structured_loss == "projective" else tl["oh"].tree_marginals
+                run(tl["p"], tl["n"], False, with_scores=False)
         return step
 
-    steps = {vn: make(vn) for vn in args.variants.split(",")}
+    steps = {}
+    for vn in args.variants.split(","):
+        steps[vn] = make(vn)
+        if tl is not None:
+            steps[vn + "+marginals"] = make(vn, "marginals")
+            steps[vn + "+tree_loss"] = make(vn, "tree_loss")
+    if tl is not None:
+        used = tl["oh"].tree_loss(tl["p"], tl["y"], tl["n"], args.structured_loss, False, tl["tn"], tl["loss"])[3]
+        print(json.dumps({"structured_loss": args.structured_loss, "b": b, "v": v, "o": 150,
+                          "used_graphs": int(used.sum().item())}), flush=True)
     for r in range(args.rounds):
         for vn, step in steps.items():
             for _ in range(10):
