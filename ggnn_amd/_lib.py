@@ -37,6 +37,7 @@ EXPORTED = (
     "ggnn_projective_marginals_workspace_bytes", "ggnn_projective_marginals", "ggnn_arc_confidence",
     "ggnn_tree_marginals_workspace_bytes", "ggnn_tree_marginals",
     "ggnn_tree_loss_workspace_bytes", "ggnn_tree_loss", "ggnn_tree_loss_dev",
+    "ggnn_tree_sample_workspace_bytes", "ggnn_tree_sample",
 )
 DECODE_COUNTS = 5   # include/ggnn.h GGNN_DECODE_COUNTS: n_kept, las, uas, lab, regular
 TREE_MAXV = 256                # include/ggnn.h GGNN_TREE_MAXV
@@ -44,6 +45,8 @@ TREE_FORBIDDEN = -2 ** 31      # include/ggnn.h GGNN_TREE_FORBIDDEN
 PROJ_LDS_MAXN = 128            # include/ggnn.h GGNN_PROJ_LDS_MAXN
 MARG_LDS_MAXN = 107            # include/ggnn.h GGNN_MARG_LDS_MAXN
 LAPL_LDS_MAXN = 199            # include/ggnn.h GGNN_LAPL_LDS_MAXN
+SAMPLE_LDS_MAXN = 199          # include/ggnn.h GGNN_SAMPLE_LDS_MAXN
+SAMPLE_MAX = 4096              # include/ggnn.h GGNN_SAMPLE_MAX
 NUM_KERNEL_KINDS = 11
 
 
@@ -166,6 +169,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
         lib.ggnn_tree_loss_dev.restype = _I
         lib.ggnn_tree_loss_dev.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32, _P,
                                            _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+        lib.ggnn_tree_sample_workspace_bytes.restype = ctypes.c_size_t
+        lib.ggnn_tree_sample_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        lib.ggnn_tree_sample.restype = _I
+        lib.ggnn_tree_sample.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, ctypes.c_int32,
+                                         ctypes.c_uint64, _P, _P, _P, _P, ctypes.c_size_t, _P]
         lib.ggnn_arc_confidence.restype = _I
         lib.ggnn_arc_confidence.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, _P, _P]
         lib.ggnn_dbg_gemm.restype = _I

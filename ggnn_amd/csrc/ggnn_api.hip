@@ -30,6 +30,7 @@
 #include "k_gemm_ring.h"
 #include "k_generic.h"
 #include "k_pairs.h"
+#include "k_tree_sample.h"
 
 // ---------------------------------------------------------------------------
 // error handling (thread-local last error; no exception crosses the ABI)
@@ -1952,6 +1953,42 @@ int ggnn_tree_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, c
   if (!target_num) return fail(GGNN_EINVAL, "tree_loss_dev: NULL target_num");
   return tree_loss_impl(d, probs_head, o, gold_head, n_nodes, family, single_root, 0.f, target_num, marg, logz, status,
                         used, loss_inout, workspace, workspace_bytes, stream);
+}
+
+// dependency trees drawn from the distribution of ggnn_tree_marginals
+// (k_tree_sample.h); booked under the heads kind
+static_assert(GGNN_SAMPLE_LDS_MAXN == SAMPLE_LDS_MAXN && GGNN_SAMPLE_MAX == SAMPLE_MAX, "tree sample constants");
+static_assert(GGNN_SAMPLE_LDS_MAXN <= GGNN_LAPL_LDS_MAXN &&
+                  sizeof(float) * (SAMPLE_LDS_MAXN - 1) * LAPL_LD(SAMPLE_LDS_MAXN - 1) <= sizeof(float) * LAPL_MAT_FLOATS &&
+                  sizeof(float) * LAPL_MAT_FLOATS + sizeof(LaplShared) <= 160 * 1024 &&
+                  sizeof(float) * SAMPLE_LDS_MAXN * LAPL_LD(SAMPLE_LDS_MAXN) + sizeof(LaplShared) > 160 * 1024,
+              "GGNN_SAMPLE_LDS_MAXN is the largest n whose matrix fits the LDS of a CU beside the side arrays");
+size_t ggnn_tree_sample_workspace_bytes(int32_t b, int32_t v, int32_t num_samples) {
+  if (b < 1 || num_samples < 1 || v <= GGNN_SAMPLE_LDS_MAXN) return 0;
+  return (size_t)b * (size_t)num_samples * 4 * (size_t)(v - 1) * (size_t)LAPL_LD(v - 1);
+}
+int ggnn_tree_sample(const ggnn_dims* d, const float* probs_head, int32_t o, const int32_t* n_nodes,
+                     int32_t single_root, const float* marg, const float* logz, const int32_t* marg_status,
+                     int32_t num_samples, uint64_t seed, int32_t* heads, float* log_prob, int32_t* status,
+                     void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  const char* const name = "tree_sample";
+  const bool null_arg = !probs_head || !n_nodes || !logz || !marg_status || !heads || !log_prob || !status;
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
+  if (num_samples < 1 || num_samples > GGNN_SAMPLE_MAX)
+    return fail(GGNN_EINVAL, "tree_sample: num_samples must lie in 1.." + std::to_string(GGNN_SAMPLE_MAX) + " (got " +
+                                 std::to_string(num_samples) + ")");
+  if (single_root && !marg) return fail(GGNN_EINVAL, "tree_sample: single_root needs marg (NULL pointer)");
+  if ((long)d->b * num_samples > 0x7FFFFFFFL) return fail(GGNN_EINVAL, "tree_sample: b * num_samples exceeds the grid");
+  const size_t need = ggnn_tree_sample_workspace_bytes(d->b, d->v, num_samples);
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_tree_sample, dim3((unsigned)(d->b * num_samples)), dim3(LAPL_THREADS), 0, s, probs_head, (int)o,
+                     (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (const int*)marg_status,
+                     (int)num_samples, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob,
+                     (int*)status, need ? (float*)workspace : nullptr, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
+  LAUNCHCHK();
+  return GGNN_OK;
 }
 
 }  // extern "C"

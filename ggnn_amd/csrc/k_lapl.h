@@ -81,10 +81,10 @@ struct LaplShared {
   double lnz;
 };
 
-// Whether a dependency tree exists over the allowed arcs (see above).  R: 2 *
-// LAPL_BIT_WORDS * TREE_MAXV words, word w of node j's row at [w * TREE_MAXV +
-// j].  Called by the whole workgroup; the same answer in every thread.
-DEV bool lapl_has_tree(unsigned* R, const float* __restrict__ P, int o, int n, int single_root, int tid) {
+// The reachability rows of a graph (see above).  R: 2 * LAPL_BIT_WORDS *
+// TREE_MAXV words, word w of node j's row at [w * TREE_MAXV + j].  Returns
+// the half of R that holds the finished rows.  Called by the whole workgroup.
+DEV const unsigned* lapl_reach(unsigned* R, const float* __restrict__ P, int o, int n, int tid) {
   const int nw = (n + 31) >> 5, half = LAPL_BIT_WORDS * TREE_MAXV;
   for (int x = tid; x < n * nw; x += LAPL_THREADS) {
     const int w = x / n, j = x - w * n;
@@ -116,7 +116,14 @@ DEV bool lapl_has_tree(unsigned* R, const float* __restrict__ P, int o, int n, i
     __syncthreads();
     cur ^= 1;
   }
-  const unsigned* A = R + cur * half;
+  return R + cur * half;
+}
+
+// Whether node tid may be the root of every word: node 0 (multi-root) or a word
+// with an allowed ROOT arc (single_root) that reaches every word.  A:
+// lapl_reach's rows.
+DEV bool lapl_root_ok(const unsigned* A, const float* __restrict__ P, int o, int n, int single_root, int tid) {
+  const int nw = (n + 31) >> 5;
   bool good = false;
   if (tid < n && (single_root ? (tid >= 1 && marg_allowed(P[(long)tid * o])) : tid == 0)) {
     good = true;
@@ -126,15 +133,24 @@ DEV bool lapl_has_tree(unsigned* R, const float* __restrict__ P, int o, int n, i
       good = good && (A[w * TREE_MAXV + tid] & need) == need;
     }
   }
-  return __syncthreads_or(good) != 0;
+  return good;
 }
 
-// The matrix, its inverse and the outputs of one graph that has a tree (S: m *
-// LAPL_LD(m) floats, LDS or global; marg / scores / logz point at the graph's
-// own outputs).  Returns 1 with the outputs written, 2 (nothing written) as
-// said above.  Called by the whole workgroup.
-DEV int lapl_solve(float* S, LaplShared& sh, const float* __restrict__ P, int o, int v, int n, int single_root,
-                   float* __restrict__ marg, int* __restrict__ scores, float* __restrict__ logz, int tid) {
+// Whether a dependency tree exists over the allowed arcs (see above).  R: as
+// lapl_reach's.  Called by the whole workgroup; the same answer in every thread.
+DEV bool lapl_has_tree(unsigned* R, const float* __restrict__ P, int o, int n, int single_root, int tid) {
+  const unsigned* A = lapl_reach(R, P, o, n, tid);
+  return __syncthreads_or(lapl_root_ok(A, P, o, n, single_root, tid)) != 0;
+}
+
+// lapl_solve in its pieces (each called by the whole workgroup; S: m *
+// LAPL_LD(m) floats, LDS or global).  lapl_build: the row sums and the matrix.
+// rho = 0: the matrix of single_root as said above.  rho >= 1 (the sampler,
+// k_tree_sample.h): the multi-root matrix of the trees whose one ROOT child is
+// word rho: r'(d) = [d == rho] and word rho's word potentials are 0, so that
+// its column is a unit column.
+DEV void lapl_build(float* S, LaplShared& sh, const float* __restrict__ P, int o, int n, int single_root, int rho,
+                    int tid) {
   const int lane = tid & 63, wave = tid >> 6;
   const int m = n - 1, LD = LAPL_LD(m);
   // ---- normalise every word's row and write its column of A (a wave per word: the reads of P are coalesced,
@@ -173,11 +189,19 @@ DEV int lapl_solve(float* S, LaplShared& sh, const float* __restrict__ P, int o,
       if (hp == dp) val = single_root ? sw / total : 1.f;
       else val = marg_allowed(p) ? -(ldexpf(p, -e) / total) : 0.f;
       if (single_root && hp == 0) val = r / total;
+      if (rho) val = (dp == rho - 1) ? (hp == dp ? 1.f : 0.f) : (hp == dp ? sw / total : val);
       S[hp * LD + dp] = val;
     }
   }
   __syncthreads();
-  // ---- Gauss-Jordan, column by column
+}
+
+// lapl_invert: the Gauss-Jordan elimination, column by column; the inverse in
+// permuted storage, the pivots in sh.pv.  Returns 2 at a pivot that is 0 or not
+// finite, else 1.
+DEV int lapl_invert(float* S, LaplShared& sh, int n, int tid) {
+  const int lane = tid & 63;
+  const int m = n - 1, LD = LAPL_LD(m);
   const int q = LAPL_THREADS / LD, rr = LAPL_THREADS - q * LD, cells = m * LD;
   const int i0 = tid / LD, j0 = tid - i0 * LD;
   for (int k = 0; k < m; ++k) {
@@ -227,7 +251,14 @@ DEV int lapl_solve(float* S, LaplShared& sh, const float* __restrict__ P, int o,
     }
     __syncthreads();
   }
-  // ---- ln Z and the determinant's sign (wave 0, double, fixed order)
+  return 1;
+}
+
+// lapl_logdet: ln Z into sh.lnz and the determinant's sign (wave 0, double,
+// fixed order).  Returns 2 when the sign is not positive or ln Z not finite.
+DEV int lapl_logdet(LaplShared& sh, int n, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int m = n - 1;
   if (wave == 0) {
     double acc = 0.0;
     int neg = 0, leaders = 0;
@@ -255,8 +286,16 @@ DEV int lapl_solve(float* S, LaplShared& sh, const float* __restrict__ P, int o,
   __syncthreads();
   const float lz = (float)sh.lnz;
   if (!sh.ctl[2] || !(fabsf(lz) <= FLT_MAX)) return 2;
-  if (tid == 0) *logz = lz;
-  // ---- the outputs, every element of [v][o] once (a wave per row)
+  return 1;
+}
+
+// lapl_emit: the outputs, every element of [v][o] once (a wave per row).
+DEV void lapl_emit(const float* S, const LaplShared& sh, const float* __restrict__ P, int o, int v, int n,
+                   int single_root, float* __restrict__ marg, int* __restrict__ scores, float* __restrict__ logz,
+                   int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int m = n - 1, LD = LAPL_LD(m);
+  if (tid == 0) *logz = (float)sh.lnz;
   for (int i = wave; i < v; i += LAPL_WAVES) {
     const bool word = i >= 1 && i < n;
     const int dp = i - 1;
@@ -292,6 +331,17 @@ DEV int lapl_solve(float* S, LaplShared& sh, const float* __restrict__ P, int o,
       if (scores) scores[at] = ok ? (int)rintf(val * MARG_SCALE) : TREE_FORBIDDEN;
     }
   }
+}
+
+// The matrix, its inverse and the outputs of one graph that has a tree (marg /
+// scores / logz point at the graph's own outputs).  Returns 1 with the outputs
+// written, 2 (nothing written) as said above.  Called by the whole workgroup.
+DEV int lapl_solve(float* S, LaplShared& sh, const float* __restrict__ P, int o, int v, int n, int single_root,
+                   float* __restrict__ marg, int* __restrict__ scores, float* __restrict__ logz, int tid) {
+  lapl_build(S, sh, P, o, n, single_root, 0, tid);
+  if (lapl_invert(S, sh, n, tid) != 1) return 2;
+  if (lapl_logdet(sh, n, tid) != 1) return 2;
+  lapl_emit(S, sh, P, o, v, n, single_root, marg, scores, logz, tid);
   return 1;
 }
 

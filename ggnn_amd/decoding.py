@@ -1,7 +1,8 @@
 """Decoding: the chain decode -> marginals -> tree / projective pass ->
-confidences, written once against a backend with the device binding's six
-methods (``decode``, ``tree_decode``, ``projective_decode``,
-``projective_marginals``, ``tree_marginals``, ``arc_confidence``):
+confidences -> samples, written once against a backend with the device
+binding's seven methods (``decode``, ``tree_decode``, ``projective_decode``,
+``projective_marginals``, ``tree_marginals``, ``arc_confidence``,
+``tree_sample``):
 heads.OutputHeads on the GPU, ``HostDecoder`` over evaluation.*_arrays for a
 model on a CPU device; and the model's decoding entries (``DecodingMixin``)."""
 from __future__ import annotations
@@ -71,8 +72,9 @@ def _in_place(host_form):
 
 
 class HostDecoder:
-    """OutputHeads' six decoding methods over the host forms, numpy in and
-    out; the marginals as float32, without the host forms' span_max / cond."""
+    """OutputHeads' seven decoding methods over the host forms, numpy in and
+    out; the marginals as float32, without the host forms' span_max / cond /
+    margin."""
     tree_decode = _in_place(_eval.tree_decode_arrays)
     projective_decode = _in_place(_eval.projective_decode_arrays)
 
@@ -90,6 +92,13 @@ class HostDecoder:
     def arc_confidence(self, marg, n_nodes, pred):
         return _eval.arc_confidence_arrays(marg, n_nodes, pred)
 
+    def tree_sample(self, probs_head, n_nodes, num_samples, seed=0, single_root=True, marginals=None):
+        """(heads int32 [b, K, v], log_prob float32 [b, K], status int32 [b, K])
+        of evaluation.tree_sample_arrays (float64; it computes its own
+        marginals, ``marginals`` is not read)."""
+        heads, log_prob, status, _ = _eval.tree_sample_arrays(probs_head, n_nodes, num_samples, seed, single_root)
+        return heads, log_prob.astype(np.float32), status
+
 
 def _select(keep, x, fill):
     """x where keep, ``fill`` elsewhere: int32, in x's own array type."""
@@ -98,7 +107,8 @@ def _select(keep, x, fill):
     return np.where(keep, x, fill).astype(np.int32)
 
 
-def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=True, confidence=False):
+def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=True, confidence=False, samples=0,
+                 sample_seed=0):
     """The decode and what follows it, in launch order and in ``backend``'s
     array type (probs [b, v, o], probs_e [b, v, oe] float32, n_nodes int32
     [b], labels: the two heads' targets or None).  mode True / "projective":
@@ -109,12 +119,16 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     that distribution's marginals (unless MBR made them) and the gather of the
     returned heads' marginals come last.  The passes and the marginals see n *
     regular; tree_status is the pass's own where a graph is regular (MBR: and
-    has marginals), 2 elsewhere."""
+    has marginals), 2 elsewhere.  samples = K > 0: K trees per graph drawn from
+    the distribution over all dependency trees (backend.tree_sample on n *
+    regular, with the "mbr" marginals where the chain has them) as
+    sampled_heads [b, K, v], sample_log_prob [b, K], sample_status [b, K] (2
+    where a graph is not regular)."""
     on_device, family, confidence = isinstance(probs, torch.Tensor), _MBR_FAMILY.get(mode), _confidence_mode(confidence)
     marginals = lambda kind: backend.projective_marginals if kind == "projective" else backend.tree_marginals
     pred, gold, counts = backend.decode([probs, probs_e], n_nodes, labels)
     regular = counts[:, 4] == 1
-    n_reg = _select(regular, n_nodes, 0) if mode or confidence else None
+    n_reg = _select(regular, n_nodes, 0) if mode or confidence or samples else None
     if family:
         marg, logz, scores, has_marg = marginals(family)(probs, n_reg, single_root)
         pred, gold, counts = backend.decode([marg, probs_e], n_nodes, labels)
@@ -130,6 +144,11 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
         if family != confidence:     # (nothing reads the integer scores)
             marg, logz, _, _ = marginals(confidence)(probs, n_reg, single_root, with_scores=False)
         out["head_confidence"], out["log_partition"] = backend.arc_confidence(marg, n_nodes, pred), logz
+    if samples:
+        have = (marg, logz, scores, has_marg) if family == "nonprojective" else None
+        heads, log_prob, status = backend.tree_sample(probs, n_reg, samples, sample_seed, single_root, have)
+        out["sampled_heads"], out["sample_log_prob"] = heads, log_prob
+        out["sample_status"] = _select(counts[:, 4:5] == 1, status, 2)
     return out
 
 
@@ -167,14 +186,16 @@ class DecodingMixin:
                 loss = self.build_loss()
         return loss
 
-    def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False):
+    def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False, samples=0,
+                        sample_seed=0):
         """_eval_forward of a feed (default: the staged one), then decode_chain
         eagerly on the same stream (never inside a captured step).  Returns a
         dict: loss (scalar tensor), ph (the staged placeholders), b, v, n_nodes
         (host int32 [b], None: masks not in closed form) and the chain's pred /
         gold / counts / tree_status / head_confidence / log_partition: device
         tensors, numpy arrays on a CPU device (HostDecoder), None without
-        n_nodes or where tree / confidence (predict_batch's) do not ask."""
+        n_nodes or where tree / confidence (predict_batch's) do not ask; with
+        samples > 0 also sampled_heads / sample_log_prob / sample_status."""
         mode = _tree_mode(tree, confidence, "_decode_forward")
         loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
         ph = dict(self.placeholders)
@@ -193,7 +214,8 @@ class DecodingMixin:
             backend, probs, probs_e = HostDecoder(), probs.numpy(), probs_e.numpy()
             labels = [np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o),
                       np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)] if with_gold else None
-        r.update(decode_chain(backend, probs, probs_e, n, labels if with_gold else None, mode, single_root, confidence))
+        r.update(decode_chain(backend, probs, probs_e, n, labels if with_gold else None, mode, single_root, confidence,
+                              samples, sample_seed))
         return r
 
     def _host_pred(self, ph, b, v):
@@ -205,7 +227,7 @@ class DecodingMixin:
                                      np.asarray(ph["node_mask"], np.float32).reshape(b, v, o),
                                      np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
 
-    def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False):
+    def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False, samples=0, sample_seed=0):
         """The predicted tree of every graph of a batch: {'heads': [b, v],
         'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
         arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
@@ -242,9 +264,21 @@ class DecodingMixin:
         tree=True or "mbr", whose trees that distribution need not contain);
         "nonprojective": over all dependency trees, with every value of tree
         (with tree="mbr" the marginals are computed once).  tree must be
-        False, True, "projective", "projective-mbr" or "mbr"."""
+        False, True, "projective", "projective-mbr" or "mbr".  samples = K > 0:
+        the dict gains 'sampled_heads' [b, K, v] int32, K trees per graph drawn
+        from the distribution over all dependency trees that the head
+        probabilities define (ggnn_tree_sample with seed sample_seed;
+        single_root: one ROOT child), -1 on node 0, padding and where the
+        status is not 1; 'sample_log_prob' [b, K] float32, ln of each tree's
+        probability (-inf where the status is not 1); 'sample_status' [b, K]
+        int32: 1 = drawn, 0 = fewer than two nodes, 2 = no tree exists, a
+        numerical dead end or not attempted (an irregular graph, a feed whose
+        masks are not in closed form).  samples = 0 launches nothing."""
         tree = _tree_mode(tree, confidence, "predict_batch")
-        r = self._decode_forward(feed_dict, False, tree, single_root, confidence)
+        samples = int(samples)
+        if not 0 <= samples <= _eval.SAMPLE_MAX:
+            raise ValueError("samples must lie in 0..%d (got %d)" % (_eval.SAMPLE_MAX, samples))
+        r = self._decode_forward(feed_dict, False, tree, single_root, confidence, samples, sample_seed)
         ph, b, v, pred = r["ph"], r["b"], r["v"], r["pred"]
         if pred is None:
             pred = self._host_pred(ph, b, v)
@@ -262,7 +296,40 @@ class DecodingMixin:
             if conf is None:                 # masks not in closed form: no marginals
                 conf, logz = np.zeros((b, v), np.float32), np.full(b, np.nan, np.float32)
             out["head_confidence"], out["log_partition"] = _as_np(conf), _as_np(logz)
+        if samples:
+            if r.get("sampled_heads") is None:      # masks not in closed form: not attempted
+                r["sampled_heads"] = np.full((b, samples, v), -1, np.int32)
+                r["sample_log_prob"] = np.full((b, samples), -np.inf, np.float32)
+                r["sample_status"] = np.full((b, samples), 2, np.int32)
+            for k in ("sampled_heads", "sample_log_prob", "sample_status"):
+                out[k] = _as_np(r[k])
         return out
+
+    def sample_trees(self, raw_data, num_samples, single_root=True, seed=0):
+        """Dependency trees of raw btb sentences (parse's input) drawn from the
+        distribution over all dependency trees that the head probabilities
+        define (predict_batch(samples=num_samples)).  Returns (trees,
+        log_probs): trees[k] a list of up to num_samples entries in the JSON's
+        'targets' form [[head, label], ...] for nodes 1..n-1 (the label
+        one-based: the label head's arg-max, which does not depend on the
+        head), log_probs[k] the ln of each one's probability, aligned.  A
+        sample whose status is not 1 is left out; a sentence
+        process_raw_graphs drops yields [].  Batch number i of the iterator
+        draws with seed (seed + i) mod 2^64: the same call gives the same
+        trees."""
+        raw = [{"targets": [], **d, "id": k} for k, d in enumerate(raw_data)]
+        out, log_probs = [[] for _ in raw], [[] for _ in raw]
+        data = self.process_raw_graphs(raw, False)
+        for i, feed in enumerate(self.make_minibatch_iterator(data, False)):
+            p = self.predict_batch(feed, False, single_root, samples=num_samples,
+                                   sample_seed=(int(seed) + i) % 2 ** 64)
+            for g, k in enumerate(p["sentences_id"]):
+                n = int(p["n_nodes"][g])
+                for s in np.nonzero(p["sample_status"][g] == 1)[0]:
+                    out[k].append([[int(h), int(l) + 1] for h, l in zip(p["sampled_heads"][g, s, 1:n],
+                                                                        p["labels"][g, 1:n])])
+                    log_probs[k].append(float(p["sample_log_prob"][g, s]))
+        return out, log_probs
 
     def parse(self, raw_data, tree=False, single_root=True, confidence=False):
         """Parse raw btb sentences (the dicts process_raw_graphs accepts;

@@ -877,14 +877,21 @@ def _has_tree(ok, n, single_root):
     may take head j"), decided on the arcs alone: without single_root every
     word is reachable from node 0 walking head -> dependent; with it some word
     with an allowed ROOT arc reaches every other word among the words."""
-    reach = ok.T | np.eye(n, dtype=bool)                # reach[j, i]: i is j or a dependent of j
+    reach = _reach(ok, n)
+    if not single_root:
+        return bool(reach[0, 1:].all())
+    return bool((ok[1:, 0] & reach[1:, 1:].all(axis=1)).any())
+
+
+def _reach(ok, n):
+    """reach[j, i]: node i is j or below j walking head -> dependent over the
+    allowed arcs ok[i, j]."""
+    reach = ok.T | np.eye(n, dtype=bool)
     hops = 1
     while hops < n:                                     # boolean squaring: paths of up to 2^t arcs
         reach = (reach.astype(np.int32) @ reach.astype(np.int32)) > 0
         hops *= 2
-    if not single_root:
-        return bool(reach[0, 1:].all())
-    return bool((ok[1:, 0] & reach[1:, 1:].all(axis=1)).any())
+    return reach
 
 
 def _laplacian(w, n, single_root):
@@ -1047,3 +1054,199 @@ def tree_loss_arrays(probs_head, gold_head, n_nodes, family, single_root, target
     used = (status == 1).astype(np.int32)
     term = float(np.sum(logz[used == 1].astype(np.float64))) / float(target_num)
     return term, marg, logz, status, used
+
+
+# ------------------------------------------------ sampling dependency trees
+# Host form of ``ggnn_tree_sample`` (include/ggnn.h, csrc/k_tree_sample.h):
+# trees drawn from the distribution over ALL dependency trees whose arc
+# marginals tree_marginals_arrays gives, by conditional (ancestral) sampling on
+# the matrix-tree inverse.  B = inverse of the multi-root matrix A (A[h][d] =
+# -w(d, h), A[d][d] = r(d) + sum_h w(d, h)); single_root first draws the one
+# ROOT child rho from marg[.][0] among the words with an allowed ROOT arc that
+# reach every word, then uses r'(d) = [d == rho] and zeroes rho's word
+# potentials.  The words are walked in ascending order; word d takes ROOT with
+# mass r'(d) B[d][d] and word h with mass w(d, h) (B[d][d] - B[d][h]) (0 for an
+# arc that is not allowed and for an h whose chain of fixed heads ends in d),
+# and the drawn head h* is conditioned on by the Sherman-Morrison update
+#   B <- B - cvec (x) B[d, :] / den,  cvec = B[:, d] - e_d - [h* > 0] B[:, h*],
+#                                     den = B[d][d] - [h* > 0] B[d][h*].
+SAMPLE_LDS_MAXN = 199          # GGNN_SAMPLE_LDS_MAXN
+SAMPLE_MAX = 4096              # GGNN_SAMPLE_MAX
+SAMPLE_STREAM = 0x40000000     # the last Philox counter word of every draw
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al. 2011) on Python integers: counter four and
+    key two 32-bit words; returns the four output words."""
+    c = [int(x) & 0xFFFFFFFF for x in counter]
+    k0, k1 = (int(x) & 0xFFFFFFFF for x in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k1, p0 & 0xFFFFFFFF]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return tuple(c)
+
+
+def sample_uniform(seed, g, s, d):
+    """The uniform of word d's draw (d = 0: the ROOT child's) in sample s of
+    graph g: the top 24 bits of Philox word x at counter (d, s, g, 0x40000000)
+    under the 64-bit seed as key, times 2^-24 (exact in fp32)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    x = philox4x32_10((d, s, g, SAMPLE_STREAM), (seed & 0xFFFFFFFF, seed >> 32))[0]
+    return (x >> 8) * 2.0 ** -24
+
+
+def _sample_pick(q, u, dt, forced=None):
+    """One draw over the masses q (>= 0, ascending column order) in dt: the
+    smallest j with q[j] > 0 and c[j] > u * S (c the inclusive prefix sums, S
+    their last), the largest j with q[j] > 0 if rounding leaves none.  Returns
+    (j, prob, margin); j = -1 when S is not > 0.  With ``forced`` that column
+    is taken (prob 0 where its mass is 0 or it is out of range)."""
+    c = np.cumsum(q, dtype=dt)
+    total = c[-1]
+    if not total > 0:
+        return -1, 0.0, np.inf
+    if forced is not None:
+        j = int(forced)
+        ok = 0 <= j < len(q) and q[j] > 0
+        return j, (float(q[j]) / float(total) if ok else 0.0), np.inf
+    pos = q > 0
+    hit = np.nonzero(pos & (c > dt.type(u) * total))[0]
+    live = np.nonzero(pos)[0]
+    j = int(hit[0]) if hit.size else int(live[-1])
+    margin = np.inf
+    if j != live[0]:
+        margin = min(margin, abs(u - float(c[j - 1]) / float(total)))
+    if j != live[-1]:
+        margin = min(margin, abs(float(c[j]) / float(total) - u))
+    return j, float(q[j]) / float(total), margin
+
+
+def tree_sample_arrays(probs_head, n_nodes, num_samples, seed, single_root=True, dtype=np.float64, forced=None):
+    """The host form of ``ggnn_tree_sample`` (include/ggnn.h): num_samples
+    dependency trees per graph, drawn from the distribution that
+    tree_marginals_arrays(probs_head, n_nodes, single_root) describes.
+    Returns (heads int32 [b, K, v], log_prob [b, K], status int32 [b, K],
+    margin float64 [b, K]).  heads: the head of word i; -1 on row 0, the rows >=
+    n and where status != 1.  log_prob: sum_d ln p[d][head_d] - ln Z in
+    float64, -inf where status != 1.  status: 1 drawn; the marginals' status (0
+    n < 2, 2 no tree) where that is not 1; 2 on a numerical dead end (a draw
+    whose masses do not sum to > 0, an update whose denominator is not finite
+    and positive).  margin: the smallest distance, over the sample's draws,
+    from u to the nearer end of the chosen head's interval of the CDF (the ends
+    at 0 and 1 do not count; inf without one): a form in another precision may
+    draw another tree only where this is small.  Sample s of graph g depends
+    on (seed, g, s) alone.  ``forced``: heads [b, v] or [b, K, v] to follow in
+    place of the draws; log_prob is then the sum of the logs of the
+    conditional probabilities met (-inf where one is 0: not a tree of the
+    distribution) and heads returns them.  Matrix and updates in ``dtype``."""
+    p = np.asarray(probs_head, np.float32)
+    if p.ndim != 3:
+        raise ValueError("probs_head must be [b, v, o]")
+    b, v, o = p.shape
+    K = int(num_samples)
+    if not 1 <= K <= SAMPLE_MAX:
+        raise ValueError("num_samples must lie in 1..%d (got %d)" % (SAMPLE_MAX, K))
+    dt = np.dtype(dtype)
+    single_root = bool(single_root)
+    marg, logz, _, m_status, _ = tree_marginals_arrays(p, n_nodes, single_root, dt)
+    nn = _node_counts(n_nodes, b, v, o)
+    if forced is not None:
+        forced = np.asarray(forced, np.int64)
+        if forced.ndim == 2:
+            forced = np.repeat(forced[:, None, :], K, axis=1)
+        if forced.shape != (b, K, v):
+            raise ValueError("forced must be [b, v] or [b, num_samples, v]")
+    heads = np.full((b, K, v), -1, np.int32)
+    log_prob = np.full((b, K), -np.inf, np.float64)
+    status = np.repeat(m_status[:, None], K, axis=1).astype(np.int32)
+    margin = np.full((b, K), np.inf, np.float64)
+    for g in range(b):
+        n = int(nn[g])
+        if m_status[g] != 1:
+            continue
+        w, ok, _ = _normalised_potentials(p[g], n, dt)
+        m = n - 1
+        roots = np.zeros(n, dt)
+        if single_root:
+            reach = _reach(ok, n)
+            cand = np.zeros(n, bool)
+            cand[1:] = ok[1:, 0] & reach[1:, 1:].all(axis=1)
+            mg = marg[g, :n, 0].astype(dt)
+            roots = np.where(cand & (mg > 0), mg, 0).astype(dt)
+        inverses = {}
+        ln_p = np.log(np.where(ok, p[g, :n, :n], 1).astype(np.float64))
+        for s in range(K):
+            f = None if forced is None else forced[g, s]
+            lp, mar, rho, dead = 0.0, np.inf, 0, False
+            if single_root:
+                want = None
+                if f is not None:
+                    took = [d for d in range(1, n) if f[d] == 0]
+                    want = took[0] if took else -1
+                rho, pr, mr = _sample_pick(roots, sample_uniform(seed, g, s, 0), dt, want)
+                if rho < 0:
+                    status[g, s] = 2
+                    continue
+                mar = min(mar, mr)
+                lp += np.log(pr) if pr > 0 else -np.inf
+                if not pr > 0:
+                    heads[g, s, 1:n] = f[1:n]
+                    continue
+            if rho not in inverses:
+                W, r = w[1:, 1:].copy(), w[1:, 0].copy()
+                if single_root:
+                    r[:] = 0
+                    r[rho - 1] = 1
+                    W[rho - 1, :] = 0
+                A = -W.T.copy()
+                A[np.arange(m), np.arange(m)] = W.sum(axis=1, dtype=dt) + r
+                inverses[rho] = (W, r, np.linalg.inv(A).astype(dt))
+            W, r, B = inverses[rho]
+            B = B.copy()
+            top = np.arange(n)
+            top[rho] = 0                                              # (rho = 0 without single_root: ROOT itself)
+            out = np.full(n, -1, np.int64)
+            if rho:
+                out[rho] = 0
+            for d in range(1, n):
+                if d == rho:
+                    continue
+                dp = d - 1
+                bdd = B[dp, dp]
+                q = np.zeros(n, dt)
+                q[0] = r[dp] * bdd
+                q[1:] = W[dp, :] * (bdd - B[dp, :])
+                q[top == d] = 0                                       # h's fixed chain ends in d: a cycle
+                q = np.where(q > 0, q, 0).astype(dt)
+                h, pr, mr = _sample_pick(q, sample_uniform(seed, g, s, d), dt, None if f is None else f[d])
+                if h < 0:
+                    dead = True
+                    break
+                mar = min(mar, mr)
+                if not pr > 0:                                        # (forced only)
+                    lp = -np.inf
+                    break
+                lp += np.log(pr)
+                out[d] = h
+                den = bdd - (B[dp, h - 1] if h > 0 else 0)
+                if not (np.isfinite(den) and den > 0):
+                    dead = True
+                    break
+                cvec = B[:, dp].copy()
+                cvec[dp] -= 1
+                if h > 0:
+                    cvec -= B[:, h - 1]
+                B -= np.outer(cvec, B[dp, :] / den)
+                top[top == d] = top[h] if h > 0 else 0
+            if dead:
+                status[g, s] = 2
+                continue
+            margin[g, s] = mar
+            if f is not None:
+                heads[g, s, 1:n] = f[1:n]
+                log_prob[g, s] = lp
+            else:
+                heads[g, s, 1:n] = out[1:]
+                log_prob[g, s] = float(np.sum(ln_p[np.arange(1, n), out[1:]])) - float(logz[g])
+    return heads, log_prob, status, margin

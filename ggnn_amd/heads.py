@@ -178,6 +178,7 @@ class OutputHeads:
         self._proj_ws = None   # ggnn_projective_decode's workspace (graphs above PROJ_LDS_MAXN nodes)
         self._marg_ws = None   # ggnn_projective_marginals' workspace (graphs above MARG_LDS_MAXN nodes)
         self._lapl_ws = None   # ggnn_tree_marginals' workspace (graphs above LAPL_LDS_MAXN nodes)
+        self._sample_ws = None  # ggnn_tree_sample's workspace (graphs above SAMPLE_LDS_MAXN nodes)
         self._loss_ws = None   # ggnn_tree_loss' workspace (n_eff, then the family's marginals workspace)
         self._saved = None
         # the last forward's structured loss (tree_loss=): the marginals that
@@ -453,6 +454,51 @@ class OutputHeads:
         own (grown on demand; needed for v > LAPL_LDS_MAXN only)."""
         return self._marginals_pass("tree_marginals", "_lapl_ws", probs_head, n_nodes, single_root, with_scores,
                                     workspace)
+
+    def tree_sample(self, probs_head, n_nodes, num_samples, seed=0, single_root=True, marginals=None, workspace=None):
+        """num_samples dependency trees per graph drawn from the distribution
+        over ALL dependency trees that the head probabilities define, on the
+        current stream (ggnn_tree_sample: conditional sampling on the
+        matrix-tree inverse).  probs_head: float32 [b, v, o]; n_nodes: int32
+        [b]; seed: a 64-bit integer (sample s of graph g depends on seed, g and
+        s alone).  marginals: what ``tree_marginals`` returned for the same
+        probs_head, n_nodes and single_root (run here when None).  Returns
+        (heads int32 [b, K, v]: the head of word i, -1 on row 0, the rows >= n
+        and where status != 1; log_prob float32 [b, K]: ln of the tree's
+        probability, -inf where status != 1; status int32 [b, K]: 1 = drawn, 0
+        = n < 2, 2 = no tree exists or a numerical dead end).  workspace: a
+        uint8 tensor to use instead of the binding's own (grown on demand;
+        needed for v > SAMPLE_LDS_MAXN only)."""
+        p = probs_head
+        _check_tensor(p, "probs_head", torch.float32)
+        b, v, o = p.shape
+        dev = p.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("tree_sample needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
+        K = int(num_samples)
+        if not 1 <= K <= _lib.SAMPLE_MAX:
+            raise ValueError("num_samples must lie in 1..%d (got %d)" % (_lib.SAMPLE_MAX, K))
+        _check_n_nodes(n_nodes, b, dev)
+        if marginals is None:
+            marginals = self.tree_marginals(p, n_nodes, single_root, with_scores=False)
+        marg, logz, _, m_status = marginals
+        if (marg.shape != p.shape or marg.dtype != torch.float32 or marg.device != dev or not marg.is_contiguous()
+                or logz.dtype != torch.float32 or logz.device != dev or logz.numel() != b or not logz.is_contiguous()):
+            raise ValueError("marginals must be tree_marginals' outputs for probs_head")
+        _check_int32(m_status, "marginals' status", (b,), dev)
+        need = int(self._lib.ggnn_tree_sample_workspace_bytes(b, v, K))
+        workspace = self._workspace("_sample_ws", need, dev, workspace)
+        heads = torch.empty(b, K, v, dtype=torch.int32, device=dev)
+        log_prob = torch.empty(b, K, dtype=torch.float32, device=dev)
+        status = torch.empty(b, K, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_tree_sample(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes), int(bool(single_root)),
+                                              _ptr(marg), _ptr(logz), _ptr(m_status), K,
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(heads), _ptr(log_prob),
+                                              _ptr(status), _ptr(workspace),
+                                              0 if workspace is None else workspace.numel(), _stream()),
+                   "ggnn_tree_sample")
+        return heads, log_prob, status
 
     def arc_confidence(self, marg, n_nodes, pred):
         """conf float32 [b, v]: marg[g, i, pred[g, i, 0]], 0 where there is no

@@ -672,6 +672,67 @@ int ggnn_tree_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, c
                        float* marg, float* logz, int32_t* status, int32_t* used, float* loss_inout,
                        void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* Dependency trees drawn from the distribution that ggnn_tree_marginals
+ * describes (weight of a tree: the product of its words' head probabilities,
+ * crossing arcs included; single_root: exactly one ROOT child): num_samples = K
+ * trees per graph.  Potentials, allowed arcs, the clamping of n and the
+ * normalised w(d, h) / r(d) are ggnn_tree_marginals'.  marg, logz and
+ * marg_status are that call's outputs for the same probs_head, n_nodes and
+ * single_root (marg is read with single_root only and may be NULL without).
+ * Conditional (ancestral) sampling on the matrix-tree inverse, no random walk:
+ * B = inverse of the multi-root matrix A[h][d] = -w(d, h), A[d][d] = r(d) +
+ * sum_h w(d, h), by ggnn_tree_marginals' pivoted Gauss-Jordan elimination.
+ * single_root first draws the one ROOT child rho with masses marg[g][d][0] over
+ * the words that have an allowed ROOT arc and reach every word (the
+ * reachability rows of the feasibility test: a structural mask), then builds A
+ * with r'(d) = [d == rho] and word rho's word potentials zeroed; rho has no
+ * step of its own.  The words d = 1..n-1 are walked in ascending order:
+ *   masses  q_0 = r'(d) B[d][d], q_h = w(d, h) (B[d][d] - B[d][h]), clamped at
+ *           0, 0 for an arc that is not allowed and for an h whose chain of
+ *           already fixed heads ends in d (it would close a cycle): a returned
+ *           sample is a tree by construction;
+ *   draw    u = (x >> 8) * 2^-24, x the first word of Philox4x32-10 at counter
+ *           (d, s, g, 0x40000000) (d = 0: the ROOT child's draw; s the sample,
+ *           g the graph) with the 64-bit seed as key (low word first).  With
+ *           inclusive prefix sums c_j in ascending column order and S the
+ *           last, the head is the smallest j with q_j > 0 and c_j > u * S, the
+ *           largest j with q_j > 0 if rounding leaves none;
+ *   update  cvec = B[:, d] - e_d - [h* > 0] B[:, h*], den = B[d][d] - [h* > 0]
+ *           B[d][h*], B <- B - cvec (x) B[d, :] / den (Sherman-Morrison).
+ * Outputs: heads[g][s][i] the head of word i, -1 on row 0, rows >= n and where
+ * status != 1; log_prob[g][s] = sum_d ln probs_head[d][head_d] - logz[g],
+ * summed in double in word order, -inf where status != 1; status[g][s] = 1
+ * drawn, marg_status[g] (0 or 2) where that is not 1, 2 on a numerical dead
+ * end (S not > 0, den not finite and positive).  Sample s of graph g depends
+ * on (seed, g, s) alone, not on num_samples.
+ * Storage: a graph with n <= GGNN_SAMPLE_LDS_MAXN keeps its matrix in LDS
+ * (ggnn_tree_marginals' budget: the side arrays lie in fields that are dead
+ * after the inversion), a larger one in `workspace`, per (graph, sample); the
+ * tier follows the graph's n.  ggnn_tree_sample_workspace_bytes(b, v, K) is 0
+ * for v <= GGNN_SAMPLE_LDS_MAXN and b * K * 4 * (v-1) * ((v-1)|1) above; a
+ * smaller workspace is rejected.  Needs v <= o, v <= GGNN_TREE_MAXV, o <= 1024,
+ * 1 <= num_samples <= GGNN_SAMPLE_MAX.  One workgroup per (graph, sample), no
+ * atomics, nothing between workgroups, every loop bounded by a function of n,
+ * every reduction and scan in a fixed order.  Stream-ordered, allocation-free,
+ * legal under stream capture, bit-reproducible; booked under the heads kernel
+ * kind. */
+#define GGNN_SAMPLE_LDS_MAXN 199
+#define GGNN_SAMPLE_MAX 4096
+size_t ggnn_tree_sample_workspace_bytes(int32_t b, int32_t v, int32_t num_samples);
+int ggnn_tree_sample(const ggnn_dims* d,           /* b, v used */
+                     const float* probs_head,      /* device [b][v][o] */
+                     int32_t o,
+                     const int32_t* n_nodes,       /* device [b] */
+                     int32_t single_root,          /* 0 / 1 */
+                     const float* marg,            /* device [b][v][o], or NULL without single_root */
+                     const float* logz,            /* device [b] */
+                     const int32_t* marg_status,   /* device [b] */
+                     int32_t num_samples, uint64_t seed,
+                     int32_t* heads,               /* device [b][K][v] out */
+                     float* log_prob,              /* device [b][K] out */
+                     int32_t* status,              /* device [b][K] out */
+                     void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */

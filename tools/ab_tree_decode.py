@@ -66,6 +66,22 @@ per line
 --epoch then scores the dev set with tree=True against tree="mbr" (time, UAS,
 repaired and infeasible graphs, fetched bytes) and parses it with tree="mbr"
 and with tree=True, confidence="nonprojective".
+
+    python tools/ab_tree_decode.py --tree-sample
+
+alternates, in one process, ggnn_tree_marginals (the yardstick: one inversion
+per graph) and ggnn_tree_sample at K = 1, 4 and 16 samples per graph on the
+marginals' outputs, and times the float64 host form
+(evaluation.tree_sample_arrays, K = 1, the first 8 graphs, scaled to the
+batch); writes its lines to profiles/tree_sample_ab.jsonl (--out) too; per line
+  lapl_ms          ggnn_tree_marginals (without scores)
+  sample_k1_ms / sample_k4_ms / sample_k16_ms   ggnn_tree_sample alone
+  sample_k*_per_round   the sampler's time per round of workgroups (b * K over
+                   the device's compute units) over the marginals' own
+  host_sample_ms   the fetch + the host form, K = 1
+  differ, samples  the K = 4 samples of the first 8 graphs that are not the
+                   float64 host form's trees (all explained: asserted)
+  log_prob_err     the largest |log_prob - float64| of those samples
 """
 import argparse
 import json
@@ -312,6 +328,53 @@ def tree_marginals_sizes(torch, sizes, emit):
             emit(out)
 
 
+def tree_sample_sizes(torch, sizes, emit):
+    from ggnn_amd import evaluation as E
+    from ggnn_amd.heads import OutputHeads
+    dev = torch.device("cuda", 0)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    oh = OutputHeads(64)
+    for (b, v, o) in sizes:
+        for regime in ("flat", "peaked", "peaked-projective"):
+            ph, _, n = batch(b, v, o, 46, regime, seed=b + v)
+            ph_d, n_d = (torch.from_numpy(x).to(dev) for x in (ph, n))
+            have = oh.tree_marginals(ph_d, n_d, True, with_scores=False)
+
+            def marginals():
+                return oh.tree_marginals(ph_d, n_d, True, with_scores=False)
+
+            def sampler(k):
+                return lambda: oh.tree_sample(ph_d, n_d, k, 1, True, have)
+
+            calls = 40 if b * v <= 2048 else 5
+            t = alternated(torch, [marginals] + [sampler(k) for k in (1, 4, 16)], calls=calls)
+            out = {"b": b, "v": v, "o": o, "regime": regime, "compute_units": cus}
+            for key, x in zip(("lapl_ms", "sample_k1_ms", "sample_k4_ms", "sample_k16_ms"), t):
+                out[key], out[key + "_min"], out[key + "_max"] = x
+            rounds = lambda groups: -(-groups // cus)
+            for k in (1, 4, 16):
+                out["sample_k%d_per_round" % k] = ((out["sample_k%d_ms" % k] / rounds(b * k))
+                                                   / (out["lapl_ms"] / rounds(b)))
+            heads, log_prob, status = oh.tree_sample(ph_d, n_d, 4, 1, True, have)
+            torch.cuda.synchronize()
+            k = min(b, 8)                                             # (the float64 host form: the first 8 graphs)
+            n_h = n[:k]
+            tm = time.perf_counter()
+            E.tree_sample_arrays(ph_d[:k].cpu().numpy(), n_h, 1, 1, True)
+            out["host_sample_ms"] = (time.perf_counter() - tm) * 1e3 * b / k
+            out["host_sample_graphs"] = k
+            h_heads, h_lp, h_status, margin = E.tree_sample_arrays(ph[:k], n_h, 4, 1, True)
+            cond = E.tree_marginals_arrays(ph[:k], n_h, True)[4]
+            assert np.array_equal(status[:k].cpu().numpy(), h_status)
+            got = heads[:k].cpu().numpy()
+            diff = (got != h_heads).any(axis=2) & (h_status == 1)
+            assert all(margin[g, s] < n_h[g] * cond[g] * 2.0 ** -24 for g, s in np.argwhere(diff))
+            same = ~diff & (h_status == 1)
+            out["samples"], out["differ"] = int((h_status == 1).sum()), int(diff.sum())
+            out["log_prob_err"] = float(np.abs(log_prob[:k].cpu().numpy().astype(np.float64) - h_lp)[same].max())
+            emit(out)
+
+
 def epoch_tree_mbr(torch, emit):
     from ggnn_amd import evaluation as E
     from ggnn_amd.batching import DATA_DIR, TRAIN_WITH_DEV, read_btb_json, wsj_model_sizes
@@ -436,8 +499,11 @@ def main():
     ap.add_argument("--tree-marginals", action="store_true",
                     help="alternate the plain decode, the MST pass, ggnn_projective_marginals, ggnn_tree_marginals "
                          "and the \"mbr\" chain (and tree=True against tree=\"mbr\" with --epoch)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tree_marginals_ab.jsonl"),
-                    help="where --tree-marginals also writes its lines")
+    ap.add_argument("--tree-sample", action="store_true",
+                    help="alternate ggnn_tree_marginals with ggnn_tree_sample at 1, 4 and 16 samples per graph")
+    ap.add_argument("--out", default=None,
+                    help="where --tree-marginals / --tree-sample also write their lines (default: profiles/"
+                         "tree_marginals_ab.jsonl / profiles/tree_sample_ab.jsonl)")
     ap.add_argument("--sizes", default="20x40x150,256x128x150")
     args = ap.parse_args()
     import torch
@@ -445,14 +511,18 @@ def main():
     head = {"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}
     print(json.dumps(head), flush=True)
     sizes = [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")]
-    if args.tree_marginals:
-        with open(args.out, "w") as f:
+    if args.tree_marginals or args.tree_sample:
+        name = "tree_sample_ab.jsonl" if args.tree_sample else "tree_marginals_ab.jsonl"
+        with open(args.out or os.path.join(ROOT, "profiles", name), "w") as f:
             def emit(line):
                 text = json.dumps(line)
                 print(text, flush=True)
                 f.write(text + "\n")
                 f.flush()
             f.write(json.dumps(head) + "\n")
+            if args.tree_sample:
+                tree_sample_sizes(torch, sizes, emit)
+                return
             tree_marginals_sizes(torch, sizes, emit)
             if args.epoch:
                 epoch_tree_mbr(torch, emit)
