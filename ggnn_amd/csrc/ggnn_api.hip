@@ -117,6 +117,8 @@ Drop make_drop(float keep, uint64_t seed, bool seed_ptr = false) {
 }
 
 int pad_v(int v) { return v <= 32 ? 32 : v <= 64 ? 64 : v <= 128 ? 128 : -1; }
+// the hidden sizes the specialised kernels (and their weight fragments) exist for
+bool spec_hidden(int h) { return h == 128 || h == 256; }
 
 int make_cfg(const ggnn_dims* d, Cfg* c) {
   if (!d) return fail(GGNN_EINVAL, "dims is NULL");
@@ -129,7 +131,7 @@ int make_cfg(const ggnn_dims* d, Cfg* c) {
   // the general path (generic_path.h); pair mode is part of it
   c->sparse = (d->flags & GGNN_SPARSE_PAIRS) != 0;
   if (c->sparse && d->h % 4) return fail(GGNN_EUNSUP, "GGNN_SPARSE_PAIRS needs hidden % 4 == 0");
-  c->generic = c->sparse || (d->flags & GGNN_GENERIC) || !(d->h == 128 || d->h == 256) || d->v > 128;
+  c->generic = c->sparse || (d->flags & GGNN_GENERIC) || !spec_hidden(d->h) || d->v > 128;
   c->pcap = c->sparse ? 4L * d->b * d->v + (long)PAIR_TILE * d->C : 0;
   const int V = c->generic ? d->v : pad_v(d->v);
   if (d->C > CHL_MAXC) return fail(GGNN_EUNSUP, "C must be <= " + std::to_string(CHL_MAXC));
@@ -181,7 +183,7 @@ PackL pack_layout(const Cfg& c) {
   memset(&L, 0, sizeof(L));
   size_t o = 0;
   const size_t H = c.H;
-  L.fast = (c.H == 128 || c.H == 256) && !(c.flags & GGNN_GENERIC);
+  L.fast = spec_hidden(c.H) && !(c.flags & GGNN_GENERIC);
   L.loW = (long)c.C * H * H;
   L.loWg = (long)4 * H * H;
   L.loWc = (long)2 * H * H;
@@ -242,18 +244,32 @@ struct WsL {
 // dropout -- the dW problem's timestep-aligned chunks: cpt chunks of KCt rows
 // per timestep, each inside ONE timestep, so k_wgrad_reduce can apply the
 // timestep's mask to the sum of its chunks (round 6: replaces the per-timestep
-// dW tiles, their fp32 G scratch and k_edge_mask_reduce)
+// dW tiles and their fp32 G scratch)
 struct WgPlan {
+  bool big;  // 256x256 tiles (k_wgrad256): hidden 256, rows a multiple of 128
   int TS;
   long KC, nchunks, tiles;
   long cpt, KCt;  // edge dropout only (else 0)
   long wgs;       // workgroups of the launch = partial tiles in the workspace
+  // dW_c runs over channel c's graph list (k_chan_graphs) instead of every
+  // row: 256x256 tiles with channel skipping, when a K chunk's share of the
+  // graphs fits the kernel's register list.  Then k_prop_bwd writes no dM^T
+  // rows for a graph's empty channels.
+  bool lists;
 };
-long wg256_kc(const Cfg& c);
+// k_wgrad256's K chunk at hidden 256 (one workgroup per CU, 128 KiB LDS
+// ring): the largest chunk that still gives >= 7/8 of the CUs a tile-chunk;
+// the problems hold 6 + C tiles of 256 x 256 (dWg 4, dWc 2, dW one per channel)
+long wg256_kc(const Cfg& c) {
+  const long N = c.N, tiles_eq = 6 + c.C;
+  long KC = 8192;
+  while (KC > 128 && ((N % KC) != 0 || tiles_eq * (N / KC) < 224)) KC /= 2;
+  return KC;
+}
 WgPlan wg_plan(const Cfg& c) {
   WgPlan w;
   const long N = c.N, H = c.H;
-  const bool big = H == 256 && N % 128 == 0;
+  const bool big = w.big = H == 256 && N % 128 == 0;
   w.TS = big ? 256 : 128;
   const long t2 = (H / w.TS) * (H / w.TS);
   w.tiles = (6 + c.C) * t2;
@@ -285,6 +301,8 @@ WgPlan wg_plan(const Cfg& c) {
     dw_chunks = (long)c.T * cpt;
   }
   w.wgs = 6 * t2 * w.nchunks + (long)c.C * t2 * dw_chunks;
+  const long per_t = c.ed ? w.cpt : w.nchunks;  // chunks a channel's graph list is split into
+  w.lists = big && !(c.flags & GGNN_DENSE_CHANNELS) && (c.b + per_t - 1) / per_t <= WG_LIST_MAX && c.V % 32 == 0;
   return w;
 }
 // rows of k_gru_bwd's per-workgroup bias partials (one row per (timestep, workgroup))
@@ -414,10 +432,8 @@ WsL ws_layout(const Cfg& c, bool training) {
     L.dMT = o;  o += C * L.nhw * T;
     L.dbp = o; o += al(T * (size_t)c.b * C * H * 4);    // per-(timestep, graph) dL/dbeta partials
     L.gmax = o; o += al(GMAX_BYTES);                      // max |dL/dh_T| (gradient scale, ggnn_common.h) + k_absmax partials
-    if (H >= 128) {                                       // deterministic K-chunk reduction of the weight gradients
-      const WgPlan w = wg_plan(c);
-      L.wpart = o; o += al((size_t)w.wgs * w.TS * w.TS * 4);
-    }
+    const WgPlan w = wg_plan(c);                          // deterministic K-chunk reduction of the weight gradients
+    L.wpart = o; o += al((size_t)w.wgs * w.TS * w.TS * 4);
     L.gbp = o; o += al((size_t)gru_bias_rows(c) * 3 * H * 4);  // k_gru_bwd's [dbg | dbc] partials
     L.sump = o; o += al((size_t)SUM_RCS * (3 * H + C * H) * 4);  // k_sum_rows' per-row-chunk sums
     // the state keep bits [T][b][512 threads] uint2 (state_bits): laid out
@@ -442,6 +458,15 @@ struct ChanL {
 ChanL chan_lists(const Cfg& c, const void* adj, const AdjL& AL) {
   if (c.flags & GGNN_DENSE_CHANNELS) return ChanL{P<int>(adj, AL.chl_all), 0};
   return ChanL{P<int>(adj, AL.chl), c.C + 1};
+}
+// the adjacency stagers' shared tail: those lists, the occupancy bytes and
+// the per-channel graph lists from the staged degrees
+template <int V>
+void stage_chan_lists(const Cfg& c, void* adj, const AdjL& L, hipStream_t s) {
+  hipLaunchKernelGGL(k_chan_list<V>, dim3(c.b), dim3(256), 0, s, P<const u16>(adj, L.deg), c.C, P<int>(adj, L.chl),
+                     P<int>(adj, L.chl_all), P<unsigned char>(adj, L.occ));
+  hipLaunchKernelGGL(k_chan_graphs, dim3(c.C), dim3(64), 0, s, P<const unsigned char>(adj, L.occ), c.b, c.C,
+                     P<int>(adj, L.cgl));
 }
 int grid1d(long n, int bs = 256) {
   const long g = (n + bs - 1) / bs;
@@ -476,13 +501,44 @@ void copy_async(float* dst, const float* src, long n, hipStream_t s) {
   hipLaunchKernelGGL(k_copy32, dim3(grid1d((n + 3) / 4)), dim3(256), 0, s, dst, src, n);
 }
 
-// ---- dispatch helpers
-// rows per GRU workgroup = 32*RT; RT capped per kernel by its VGPR budget
-int gru_rt(const Cfg& c, int maxrt) {
+// ---- dispatch helpers: f(IC<x>{}) with a run-time choice as a compile-time
+// constant (read back as decltype(arg)::value)
+template <int X> using IC = std::integral_constant<int, X>;
+template <class F> auto by_prec(int prec, F&& f) {
+  switch (prec) {
+    case PREC_SPLIT: return f(IC<PREC_SPLIT>{});
+    case PREC_F16: return f(IC<PREC_F16>{});
+    default: return f(IC<PREC_BF16>{});
+  }
+}
+template <class F> void by_v(int V, F&& f) {  // the padded graph size (pad_v)
+  if (V == 32) f(IC<32>{});
+  else if (V == 64) f(IC<64>{});
+  else f(IC<128>{});
+}
+template <class F> void by_h(int H, F&& f) {  // the specialised hidden sizes (spec_hidden)
+  if (H == 128) f(IC<128>{});
+  else f(IC<256>{});
+}
+// the adjacency stagers' padded V x limb format (f16 unless the bf16 mode)
+template <class F> void by_v_limb(const Cfg& c, F&& f) {
+  by_v(c.V, [&](auto v) {
+    if (c.prec != PREC_BF16) f(v, std::true_type{});
+    else f(v, std::false_type{});
+  });
+}
+// rows per GRU workgroup = 32*RT; RT capped per kernel by its VGPR budget: 2
+// in the fp32-parity mode; the fused GRU backward at H = 256 keeps a1/a2
+// (2 x 16 x RT fp32 registers) live through both products and spills at RT = 4.
+constexpr int kSplitRT = 2;
+constexpr int gru_max_rt(bool bwd, int H, int prec) { return prec == PREC_SPLIT ? kSplitRT : bwd && H == 256 ? 2 : 4; }
+template <int MAXRT, class F> void by_gru_rt(const Cfg& c, F&& f) {
   const long t = c.N / 32;
-  if (maxrt >= 4 && t % 4 == 0) return 4;
-  if (maxrt >= 2 && t % 2 == 0) return 2;
-  return 1;
+  if constexpr (MAXRT >= 4) {  // (pruned: RT = 4 is not instantiated past a kernel's cap)
+    if (t % 4 == 0) return f(IC<4>{});
+  }
+  if (t % 2 == 0) return f(IC<2>{});
+  f(IC<1>{});
 }
 
 template <int V, int H, int PREC>
@@ -492,26 +548,6 @@ void launch_prop_fwd(const Cfg& c, int t, const void* hs, const u16* Ab, ChanL c
   hipLaunchKernelGGL((k_prop_fwd<V, H, PREC>), dim3(c.b), dim3(2 * H), 0, s, (const ActT<PREC>*)hs, Ab, chl.p, chl.stride,
                      P<u16>(pk, PL.wf(c.ed ? t : 0)), PL.loW, P<float>(pk, PL.beta), (ActT<PREC>*)Xa, (u16*)XT, c.C, c.N);
 }
-// k_wgrad256's K chunk at hidden 256 (one workgroup per CU, 128 KiB LDS
-// ring): the largest chunk that still gives >= 7/8 of the CUs a tile-chunk;
-// the problems hold 6 + C tiles of 256 x 256 (dWg 4, dWc 2, dW one per channel)
-long wg256_kc(const Cfg& c) {
-  const long N = c.N, tiles_eq = 6 + c.C;
-  long KC = 8192;
-  while (KC > 128 && ((N % KC) != 0 || tiles_eq * (N / KC) < 224)) KC /= 2;
-  return KC;
-}
-// whether dW_c runs over channel c's graph list (k_chan_graphs) instead of
-// every row: the specialised path at hidden 256 with channel skipping, when a
-// K chunk's share of the graphs fits the kernel's register list.  Then
-// k_prop_bwd writes no dM^T rows for a graph's empty channels.
-bool wgrad_lists(const Cfg& c) {
-  if (!(c.H == 256 && c.N % 128 == 0) || (c.flags & GGNN_DENSE_CHANNELS)) return false;
-  const WgPlan w = wg_plan(c);
-  const long per_t = c.ed ? w.cpt : w.nchunks;  // chunks a channel's graph list is split into
-  return (c.b + per_t - 1) / per_t <= WG_LIST_MAX && c.V % 32 == 0;
-}
-
 // k_prop_bwd's dh += dM W_c^T with its limb corrections on the fp8 MFMA
 // (ggnn_common.h mfma_f8corr): the fp32-parity mode, hidden a multiple of 32
 bool prop_f8(const Cfg& c) { return c.prec == PREC_SPLIT && c.H % 32 == 0; }
@@ -519,13 +555,14 @@ bool prop_f8(const Cfg& c) { return c.prec == PREC_SPLIT && c.H % 32 == 0; }
 template <int V, int H, int PREC>
 void launch_prop_bwd(const Cfg& c, int t, const void* dXT, const u16* AbT, const u16* deg, ChanL chl,
                      const PackL& PL, const void* pk, const float* dh_in, float* dh_out, void* dMT, float* dbp,
-                     const uint32_t* gmax, const uint2* sbits, hipStream_t s) {
+                     const uint32_t* gmax, bool zdm, const uint2* sbits, hipStream_t s) {
   Prof p(K_PROP_BWD, s);
-  // (the forward's state keep bits: 128-row graphs at hidden 256 only)
+  // (zdm: dM^T rows of a graph's empty channels are zero-filled, !WgPlan::lists;
+  // the forward's state keep bits: 128-row graphs at hidden 256 only)
   hipLaunchKernelGGL((k_prop_bwd<V, H, PREC>), dim3(c.b), dim3(2 * H), 0, s, (const ActT<PREC>*)dXT, AbT, deg, chl.p,
                      chl.stride,
                      P<u16>(pk, PL.wt(c.ed ? t : 0)), PL.loW, dh_in, dh_out, (u16*)dMT, dbp, c.C, c.N, c.sdrop, t - 1,
-                     gmax, (int)!wgrad_lists(c), (V == 128 && H == 256) ? sbits : (const uint2*)nullptr);
+                     gmax, (int)zdm, (V == 128 && H == 256) ? sbits : (const uint2*)nullptr);
 }
 template <int H, int RT, int PREC>
 void launch_gru_fwd(const Cfg& c, int t, const void* Xa, const u16* hb, const float* hf, const PackL& PL,
@@ -558,53 +595,6 @@ void launch_gru_bwd(const Cfg& c, const float* delta, const float* hf, const flo
 }
 long gru_bias_rows(const Cfg& c) { return (long)c.T * std::max<long>(c.N / 32, 1); }
 
-#define DISPATCH_V(c, FN, H, PREC, ...)                 \
-  do {                                                  \
-    if ((c).V == 32) FN<32, H, PREC>(__VA_ARGS__);      \
-    else if ((c).V == 64) FN<64, H, PREC>(__VA_ARGS__); \
-    else FN<128, H, PREC>(__VA_ARGS__);                 \
-  } while (0)
-#define DISPATCH_VH(c, FN, PREC, ...)                                  \
-  do {                                                                 \
-    if ((c).H == 64) DISPATCH_V(c, FN, 64, PREC, __VA_ARGS__);         \
-    else if ((c).H == 128) DISPATCH_V(c, FN, 128, PREC, __VA_ARGS__);  \
-    else DISPATCH_V(c, FN, 256, PREC, __VA_ARGS__);                    \
-  } while (0)
-#define DISPATCH_RT(c, FN, H, PREC, ...)                                             \
-  do {                                                                               \
-    constexpr bool sp_ = Prec<PREC>::split;                                          \
-    constexpr int mx_ = sp_ ? kSplitRT<FN##_tag>::value : kMaxRT<FN##_tag, H>::value; \
-    const int rt_ = gru_rt(c, mx_);                                                  \
-    if (mx_ >= 4 && rt_ == 4) FN<H, mx_ >= 4 ? 4 : 2, PREC>(__VA_ARGS__);            \
-    else if (rt_ == 2) FN<H, 2, PREC>(__VA_ARGS__);                                  \
-    else FN<H, 1, PREC>(__VA_ARGS__);                                                \
-  } while (0)
-#define DISPATCH_HRT(c, FN, PREC, ...)                                 \
-  do {                                                                 \
-    if ((c).H == 64) DISPATCH_RT(c, FN, 64, PREC, __VA_ARGS__);        \
-    else if ((c).H == 128) DISPATCH_RT(c, FN, 128, PREC, __VA_ARGS__); \
-    else DISPATCH_RT(c, FN, 256, PREC, __VA_ARGS__);                   \
-  } while (0)
-
-// RT caps: the fused GRU backward at H = 256 keeps a1/a2 (2 x 16 x RT fp32
-// registers) live through both products and spills at RT = 4.
-struct launch_gru_fwd_tag {};
-struct launch_gru_bwd_tag {};
-template <typename TAG, int H> struct kMaxRT { static constexpr int value = 4; };
-template <typename TAG> struct kSplitRT { static constexpr int value = 2; };
-template <> struct kMaxRT<launch_gru_bwd_tag, 256> { static constexpr int value = 2; };
-
-void launch_pack(bool f16, const float* S, int ldS, long sS, int K, int N, int trans, u16* out, long sO, long lo,
-                 int batch, hipStream_t s, Drop dr = Drop{0, 0, 0, 1.0f}, int t = 0) {
-  const int total = (N / 32) * (K / 16) * 64;
-  Prof p(K_PACK, s);
-  if (f16)
-    hipLaunchKernelGGL(k_pack_B<true>, dim3((total + 255) / 256, batch), dim3(256), 0, s, S, ldS, sS, K, N, trans, out,
-                       sO, lo, dr, t);
-  else
-    hipLaunchKernelGGL(k_pack_B<false>, dim3((total + 255) / 256, batch), dim3(256), 0, s, S, ldS, sS, K, N, trans, out,
-                       sO, lo, dr, t);
-}
 const Drop kNoDrop = {0, 0, 0, 1.0f};
 
 // -------------------------------------------------------------------- forward
@@ -687,15 +677,22 @@ int forward_impl(const Cfg& c, const void* pack, const void* adj, void* ws, bool
     u16* hb_out = SPLIT ? nullptr : P<u16>(ws, L.hb[(t + 1) & 1]);
     const void* hs = SPLIT ? (const void*)hf_in : (const void*)hb_in;
     void* XT = tr ? P<void>(ws, L.XT + L.nhw * t) : nullptr;
-    DISPATCH_VH(c, launch_prop_fwd, PREC, c, t, hs, P<u16>(adj, AL.Ab), chan_lists(c, adj, AL), PL, pack,
-                P<void>(ws, L.Xa), XT, s);
     void* hTo = (tr && t + 1 < c.T) ? P<void>(ws, L.hT + L.nhw * (t + 1)) : nullptr;
     float* ro = tr ? P<float>(ws, L.r + L.nh4 * t) : nullptr;
     float* uo = tr ? P<float>(ws, L.u + L.nh4 * t) : nullptr;
     float* co = tr ? P<float>(ws, L.c + L.nh4 * t) : nullptr;
     void* rhT = tr ? P<void>(ws, L.rhT + L.nhw * t) : nullptr;
-    DISPATCH_HRT(c, launch_gru_fwd, PREC, c, t, P<void>(ws, L.Xa), hb_in, hf_in, PL, pack, hf_out, hb_out, hTo, ro, uo,
-                 co, rhT, s);
+    by_h(c.H, [&](auto h) {
+      constexpr int HH = decltype(h)::value;
+      by_v(c.V, [&](auto v) {
+        launch_prop_fwd<decltype(v)::value, HH, PREC>(c, t, hs, P<u16>(adj, AL.Ab), chan_lists(c, adj, AL), PL, pack,
+                                                      P<void>(ws, L.Xa), XT, s);
+      });
+      by_gru_rt<gru_max_rt(false, HH, PREC)>(c, [&](auto rt) {
+        launch_gru_fwd<HH, decltype(rt)::value, PREC>(c, t, P<void>(ws, L.Xa), hb_in, hf_in, PL, pack, hf_out, hb_out,
+                                                      hTo, ro, uo, co, rhT, s);
+      });
+    });
   }
   const float* hfin = tr ? P<float>(ws, L.hfT + L.nh4 * c.T) : P<float>(ws, L.hf[c.T & 1]);
   if (!dense) {
@@ -708,8 +705,89 @@ int forward_impl(const Cfg& c, const void* pack, const void* adj, void* ws, bool
 }
 
 // ------------------------------------------------------------------- backward
+// Weight gradients over all timesteps: out[m][n] = sum_{t,rows} P_t[m][row]
+// Q_t[n][row], one grouped launch (k_wgrad.h) laid out by the caller's plan.
+// The outputs are STORED, not accumulated (k_wgrad_reduce writes each element
+// once, already unscaled).
 template <int PREC>
-int wgrad_impl(const Cfg& c, void* ws, int t0, int nt, float* dW, float* dWg, float* dWc, hipStream_t s);
+int wgrad_impl(const Cfg& c, const WsL& L, const AdjL& AL, const WgPlan& wp, const void* adj, void* ws, float* dW,
+               float* dWg, float* dWc, hipStream_t s) {
+  const long N = c.N, H = c.H;
+  WgArgs a;
+  memset(&a, 0, sizeof(a));
+  int np = 0, tiles = 0;
+  const long sa = (long)(L.nhw / 2);  // elements of one [H][N] weight-gradient operand array
+  const int TS = wp.TS;               // 256 (k_wgrad256: every problem has M = 256) or 128
+  int wgs = 0;
+  auto add = [&](size_t Poff, long stepP, size_t Qoff, long stepQ, float* out, int ldO, int M, int Nn, int nb = 1,
+                 long sQb = 0, long sOb = 0) {
+    WgProb& p = a.p[np++];
+    p.P = P<u16>(ws, Poff);
+    p.Q = P<u16>(ws, Qoff);
+    p.out = out;
+    p.ldP = N; p.ldQ = N; p.stepP = stepP; p.stepQ = stepQ; p.sQb = sQb; p.sOb = sOb;
+    p.ldO = ldO; p.M = M; p.N = Nn; p.tiles_n = Nn / TS; p.tiles_b = (M / TS) * p.tiles_n;
+    p.sPb = 0; p.pdiv = 1; p.T = c.T;
+    p.tile_begin = tiles;
+    tiles += nb * p.tiles_b;
+    p.nch = (int)wp.nchunks;
+    p.cpt = 0;
+    p.KCt = 0;
+    p.wg_begin = wgs;
+    wgs += nb * p.tiles_b * p.nch;
+  };
+  // d gates_kernel: rows [0,H) from X, rows [H,2H) from h ; columns dzg (2H)
+  add(L.XT, sa, L.dzgT, 2 * sa, dWg, 2 * H, H, 2 * H);
+  add(L.hT, sa, L.dzgT, 2 * sa, dWg + H * 2 * H, 2 * H, H, 2 * H);
+  // d candidate_kernel: rows [0,H) from X, rows [H,2H) from r*h ; columns dzc (H)
+  add(L.XT, sa, L.dzcT, sa, dWc, H, H, H);
+  add(L.rhT, sa, L.dzcT, sa, dWc + H * H, H, H, H);
+  // d edge_weights[c] = sum_t mask_t/keep (h_t^T dM_{c,t}): one problem batched
+  // over the C channels.  Under edge dropout its K chunks are timestep-aligned
+  // (wp.cpt chunks of wp.KCt rows per timestep): k_wgrad_reduce sums each
+  // timestep's chunks, applies that timestep's mask (Philox, as the pack drew
+  // it) and adds the timesteps in order
+  add(L.hT, sa, L.dMT, c.C * sa, dW, H, H, H, c.C, sa, (long)H * H);
+  WgProb& q = a.p[np - 1];
+  if (c.ed) {
+    q.cpt = (int)wp.cpt;
+    q.KCt = (int)wp.KCt;
+    q.nch = (int)(c.T * wp.cpt);
+    wgs = q.wg_begin + c.C * q.tiles_b * q.nch;
+    a.edrop = c.edrop;
+  }
+  if (wp.lists) {  // dW_c over the rows of channel c's graphs only
+    q.gl = P<const int>(adj, AL.cgl);
+    q.gls = c.b + 1;
+    q.glmod = c.C;
+    q.V32 = c.V / 32;
+  }
+  constexpr int WP = WgradPrec<PREC>::value;
+  a.nprob = np;
+  a.H = (int)H;
+  // (the workspace was sized from the plan by an earlier call)
+  if (wp.tiles != tiles || wp.wgs != wgs)
+    return fail(GGNN_EINVAL, "weight gradients: launch plan and workspace disagree");
+  if (N % wp.KC || (wp.big && wp.KC % 128)) return fail(GGNN_EUNSUP, "rows not divisible into weight-gradient chunks");
+  if (wp.big && tiles != 6 + c.C) return fail(GGNN_EINVAL, "k_wgrad256: unexpected problem set");
+  // deterministic reduction over the K chunks (k_wgrad_reduce): the partial
+  // tiles live in the workspace
+  a.part = P<float>(ws, L.wpart);
+  a.gmax = P<const uint32_t>(ws, L.gmax);  // outputs / S (the backward's gradient scale)
+  a.KC = (int)wp.KC;
+  a.nchunks = (int)wp.nchunks;
+  Prof p(K_WGRAD, s);
+  if (wp.big) {
+    hipLaunchKernelGGL((k_wgrad256<WP>), dim3(wgs), dim3(512), 0, s, a);
+    hipLaunchKernelGGL(k_wgrad_reduce<256>, dim3(tiles * 64), dim3(256), 0, s, a);
+  } else {
+    if (wp.KC % 64 != 0 || wp.KCt % 64 != 0) hipLaunchKernelGGL((k_wgrad<32, WP>), dim3(wgs), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_wgrad<64, WP>), dim3(wgs), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_wgrad_reduce<128>, dim3(tiles * 16), dim3(256), 0, s, a);
+  }
+  LAUNCHCHK();
+  return GGNN_OK;
+}
 
 // gradient accumulators zeroed by grouped k_zero_multi launches (flushed when
 // the job table fills and on scope exit)
@@ -737,8 +815,8 @@ int backward_impl(const Cfg& c, const void* pack, const void* adj, void* ws, con
   const PackL PL = pack_layout(c);
   const AdjL AL = adj_layout(c);
   const long N = c.N, H = c.H;
+  const WgPlan wp = wg_plan(c);
   const bool use_bias = (c.flags & GGNN_USE_EDGE_BIAS) != 0;
-  if (H < 128) return fail(GGNN_EUNSUP, "weight gradients need hidden >= 128");
 
   // (the weight and bias gradients need no clearing: k_wgrad_reduce and
   // k_sum_rows store every element once)
@@ -770,21 +848,29 @@ int backward_impl(const Cfg& c, const void* pack, const void* adj, void* ws, con
     const bool first = t == c.T - 1 && in_place, last = t == 0 && dense;
     const float* delta = first ? dhT : dA;
     float* dh_out = last ? dh0 : dA;
-    DISPATCH_HRT(c, launch_gru_bwd, PREC, c, delta, P<float>(ws, L.hfT + L.nh4 * t), P<float>(ws, L.r + L.nh4 * t),
-                 P<float>(ws, L.u + L.nh4 * t), P<float>(ws, L.c + L.nh4 * t), PL, pack, P<void>(ws, L.dXT), dB,
-                 P<void>(ws, L.dzcT + L.nhw * t), P<void>(ws, L.dzgT + 2 * L.nhw * t), dbc, dbg,
-                 first ? gmax : (const uint32_t*)nullptr, P<float>(ws, L.gbp) + (size_t)t * gb_stride * 3 * H,
-                 (first && c.sd) ? sb + (size_t)t * c.b * 512 : (const uint2*)nullptr, &gb_nwg, s);
-    DISPATCH_VH(c, launch_prop_bwd, PREC, c, t, P<void>(ws, L.dXT), P<u16>(adj, AL.AbT), P<u16>(adj, AL.deg),
-                chan_lists(c, adj, AL), PL, pack,
-                dB, dh_out, P<void>(ws, L.dMT + (size_t)c.C * L.nhw * t),
-                use_bias ? P<float>(ws, L.dbp) + (size_t)t * c.b * c.C * c.H : nullptr,
-                last ? gmax : (const uint32_t*)nullptr, sb, s);
+    by_h(c.H, [&](auto h) {
+      constexpr int HH = decltype(h)::value;
+      by_gru_rt<gru_max_rt(true, HH, PREC)>(c, [&](auto rt) {
+        launch_gru_bwd<HH, decltype(rt)::value, PREC>(
+            c, delta, P<float>(ws, L.hfT + L.nh4 * t), P<float>(ws, L.r + L.nh4 * t), P<float>(ws, L.u + L.nh4 * t),
+            P<float>(ws, L.c + L.nh4 * t), PL, pack, P<void>(ws, L.dXT), dB, P<void>(ws, L.dzcT + L.nhw * t),
+            P<void>(ws, L.dzgT + 2 * L.nhw * t), dbc, dbg, first ? gmax : (const uint32_t*)nullptr,
+            P<float>(ws, L.gbp) + (size_t)t * gb_stride * 3 * H,
+            (first && c.sd) ? sb + (size_t)t * c.b * 512 : (const uint2*)nullptr, &gb_nwg, s);
+      });
+      by_v(c.V, [&](auto v) {
+        launch_prop_bwd<decltype(v)::value, HH, PREC>(
+            c, t, P<void>(ws, L.dXT), P<u16>(adj, AL.AbT), P<u16>(adj, AL.deg), chan_lists(c, adj, AL), PL, pack, dB,
+            dh_out, P<void>(ws, L.dMT + (size_t)c.C * L.nhw * t),
+            use_bias ? P<float>(ws, L.dbp) + (size_t)t * c.b * c.C * c.H : nullptr,
+            last ? gmax : (const uint32_t*)nullptr, !wp.lists, sb, s);
+      });
+    });
   }
   // all weight gradients in one grouped launch over every timestep (measured:
   // 20 % faster than one launch per timestep right after its producers, whose
   // operands would still sit in the Infinity Cache)
-  if (int e = wgrad_impl<PREC>(c, adj, ws, 0, c.T, dW, dWg, dWc, s)) return e;
+  if (int e = wgrad_impl<PREC>(c, L, AL, wp, adj, ws, dW, dWg, dWc, s)) return e;
   {
     Prof p(K_IO, s);
     if (!dense)
@@ -801,105 +887,6 @@ int backward_impl(const Cfg& c, const void* pack, const void* adj, void* ws, con
     if (int e = sp.launch(s)) return e;
   }
 
-  LAUNCHCHK();
-  return GGNN_OK;
-}
-
-// Weight gradients of timesteps [t0, t0 + nt): out[m][n] = sum_{t,rows}
-// P_t[m][row] Q_t[n][row], one grouped launch (k_wgrad.h).  The outputs are
-// STORED, not accumulated (k_wgrad_reduce writes each element once, already
-// unscaled): the one caller passes all timesteps at once (t0 = 0, nt = T).
-template <int PREC>
-int wgrad_impl(const Cfg& c, const void* adj, void* ws, int t0, int nt, float* dW, float* dWg, float* dWc,
-               hipStream_t s) {
-  const WsL L = ws_layout(c, true);
-  const long N = c.N, H = c.H;
-  if (H < 128) return fail(GGNN_EUNSUP, "weight gradients need hidden >= 128");
-  if (t0 != 0 || nt != c.T) return fail(GGNN_EINVAL, "weight gradients: stored over all timesteps at once");
-  WgArgs a;
-  memset(&a, 0, sizeof(a));
-  int np = 0, tiles = 0;
-  const long sa = (long)(L.nhw / 2);  // elements of one [H][N] weight-gradient operand array
-  // 256x256 tiles (k_wgrad256) at hidden = 256: every problem has M = 256
-  const bool big = H == 256 && N % 128 == 0;
-  const int TS = big ? 256 : 128;
-  const WgPlan wp = wg_plan(c);
-  int wgs = 0;
-  auto add = [&](size_t Poff, long stepP, size_t Qoff, long stepQ, float* out, int ldO, int M, int Nn, int nb = 1,
-                 long sQb = 0, long sOb = 0) {
-    WgProb& p = a.p[np++];
-    p.P = P<u16>(ws, Poff) + (long)t0 * stepP;
-    p.Q = P<u16>(ws, Qoff) + (long)t0 * stepQ;
-    p.out = out;
-    p.ldP = N; p.ldQ = N; p.stepP = stepP; p.stepQ = stepQ; p.sQb = sQb; p.sOb = sOb;
-    p.ldO = ldO; p.M = M; p.N = Nn; p.tiles_n = Nn / TS; p.tiles_b = (M / TS) * p.tiles_n;
-    p.sPb = 0; p.pdiv = 1; p.T = nt;
-    p.tile_begin = tiles;
-    tiles += nb * p.tiles_b;
-    p.nch = (int)wp.nchunks;
-    p.cpt = 0;
-    p.KCt = 0;
-    p.wg_begin = wgs;
-    wgs += nb * p.tiles_b * p.nch;
-  };
-  // d gates_kernel: rows [0,H) from X, rows [H,2H) from h ; columns dzg (2H)
-  add(L.XT, sa, L.dzgT, 2 * sa, dWg, 2 * H, H, 2 * H);
-  add(L.hT, sa, L.dzgT, 2 * sa, dWg + H * 2 * H, 2 * H, H, 2 * H);
-  // d candidate_kernel: rows [0,H) from X, rows [H,2H) from r*h ; columns dzc (H)
-  add(L.XT, sa, L.dzcT, sa, dWc, H, H, H);
-  add(L.rhT, sa, L.dzcT, sa, dWc + H * H, H, H, H);
-  // d edge_weights[c] = sum_t mask_t/keep (h_t^T dM_{c,t}): one problem batched
-  // over the C channels.  Under edge dropout its K chunks are timestep-aligned
-  // (wp.cpt chunks of wp.KCt rows per timestep): k_wgrad_reduce sums each
-  // timestep's chunks, applies that timestep's mask (Philox, as the pack drew
-  // it) and adds the timesteps in order
-  add(L.hT, sa, L.dMT, c.C * sa, dW, H, H, H, c.C, sa, (long)H * H);
-  if (c.ed) {
-    WgProb& q = a.p[np - 1];
-    q.cpt = (int)wp.cpt;
-    q.KCt = (int)wp.KCt;
-    q.nch = (int)(nt * wp.cpt);
-    wgs = q.wg_begin + c.C * q.tiles_b * q.nch;
-    a.edrop = c.edrop;
-  }
-  constexpr int WP = WgradPrec<PREC>::value;
-  a.nprob = np;
-  a.H = (int)H;
-  if (wp.tiles != tiles || wp.wgs != wgs || wp.TS != TS)
-    return fail(GGNN_EINVAL, "weight gradients: launch plan and workspace disagree");
-  // deterministic reduction over the K chunks (k_wgrad_reduce): the partial
-  // tiles live in the workspace
-  a.part = P<float>(ws, L.wpart);
-  a.gmax = P<const uint32_t>(ws, L.gmax);  // outputs / S (the backward's gradient scale)
-  if (big) {
-    const long KC = wp.KC;
-    if (N % KC || KC % 128) return fail(GGNN_EUNSUP, "rows not divisible into weight-gradient chunks");
-    if (tiles != 6 + c.C) return fail(GGNN_EINVAL, "k_wgrad256: unexpected problem set");
-    a.KC = (int)KC;
-    a.nchunks = (int)(N / KC);
-    if (wgrad_lists(c)) {
-      // dW_c over the rows of channel c's graphs only (the last problem)
-      WgProb& q = a.p[np - 1];
-      q.gl = P<const int>(adj, adj_layout(c).cgl);
-      q.gls = c.b + 1;
-      q.glmod = c.C;
-      q.V32 = c.V / 32;
-    }
-    Prof p(K_WGRAD, s);
-    hipLaunchKernelGGL((k_wgrad256<WP>), dim3(wgs), dim3(512), 0, s, a);
-    hipLaunchKernelGGL(k_wgrad_reduce<256>, dim3(tiles * 64), dim3(256), 0, s, a);
-    return GGNN_OK;
-  }
-  const int KC = (int)wp.KC;
-  if (N % KC) return fail(GGNN_EUNSUP, "rows not divisible into weight-gradient chunks");
-  a.KC = KC;
-  a.nchunks = (int)(N / KC);
-  {
-    Prof p(K_WGRAD, s);
-    if (KC % 64 != 0 || wp.KCt % 64 != 0) hipLaunchKernelGGL((k_wgrad<32, WP>), dim3(wgs), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_wgrad<64, WP>), dim3(wgs), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_wgrad_reduce<128>, dim3(tiles * 16), dim3(256), 0, s, a);
-  }
   LAUNCHCHK();
   return GGNN_OK;
 }
@@ -1201,23 +1188,16 @@ int ggnn_set_adjacency_edges(const ggnn_dims* d, void* adj, const int32_t* edges
   fill_async(P<u16>(adj, L.Ab), 0, tiles * c.V * c.V * 2, s);
   fill_async(P<u16>(adj, L.AbT), 0, tiles * c.V * c.V * 2, s);
   const int grid = grid1d(std::max<int64_t>(num_edges, 1));
-#define ADJ_EDGES(VV, F)                                                                                         \
-  do {                                                                                                           \
-    if (num_edges > 0)                                                                                           \
-      hipLaunchKernelGGL((k_adj_from_edges<VV, F>), dim3(grid), dim3(256), 0, s, edges, graph_offsets, c.b,      \
-                         c.vin, num_edge_types, P<u16>(adj, L.Ab), P<u16>(adj, L.AbT));                           \
-    hipLaunchKernelGGL((k_adj_deg<VV, F>), dim3((unsigned)tiles), dim3(VV), 0, s, P<const u16>(adj, L.Ab),        \
-                       P<u16>(adj, L.deg));                                                                      \
-    hipLaunchKernelGGL(k_chan_list<VV>, dim3(c.b), dim3(256), 0, s, P<const u16>(adj, L.deg), c.C,               \
-                       P<int>(adj, L.chl), P<int>(adj, L.chl_all), P<unsigned char>(adj, L.occ));                \
-    hipLaunchKernelGGL(k_chan_graphs, dim3(c.C), dim3(64), 0, s, P<const unsigned char>(adj, L.occ), c.b, c.C,   \
-                       P<int>(adj, L.cgl));                                                                      \
-  } while (0)
-  const bool f16 = c.prec != PREC_BF16;
-  if (c.V == 32) { if (f16) ADJ_EDGES(32, true); else ADJ_EDGES(32, false); }
-  else if (c.V == 64) { if (f16) ADJ_EDGES(64, true); else ADJ_EDGES(64, false); }
-  else { if (f16) ADJ_EDGES(128, true); else ADJ_EDGES(128, false); }
-#undef ADJ_EDGES
+  by_v_limb(c, [&](auto v, auto f16) {
+    constexpr int V = decltype(v)::value;
+    constexpr bool F16 = decltype(f16)::value;
+    if (num_edges > 0)
+      hipLaunchKernelGGL((k_adj_from_edges<V, F16>), dim3(grid), dim3(256), 0, s, edges, graph_offsets, c.b, c.vin,
+                         num_edge_types, P<u16>(adj, L.Ab), P<u16>(adj, L.AbT));
+    hipLaunchKernelGGL((k_adj_deg<V, F16>), dim3((unsigned)tiles), dim3(V), 0, s, P<const u16>(adj, L.Ab),
+                       P<u16>(adj, L.deg));
+    stage_chan_lists<V>(c, adj, L, s);
+  });
   LAUNCHCHK();
   return GGNN_OK;
 }
@@ -1237,25 +1217,12 @@ int ggnn_set_adjacency(const ggnn_dims* d, void* adj, const float* A, ggnn_strea
   const AdjL L = adj_layout(c);
   const dim3 grid((unsigned)(c.b * c.C));
   Prof p(K_ADJ, s);
-#define PREP_ADJ(VV, F)                                                                                       \
-  do {                                                                                                        \
-    hipLaunchKernelGGL((k_prep_adj<VV, F>), grid, dim3(256), 0, s, A, c.vin, P<u16>(adj, L.Ab),                 \
-                       P<u16>(adj, L.AbT), P<u16>(adj, L.deg));                                               \
-    hipLaunchKernelGGL(k_chan_list<VV>, dim3(c.b), dim3(256), 0, s, P<const u16>(adj, L.deg), c.C,             \
-                       P<int>(adj, L.chl), P<int>(adj, L.chl_all), P<unsigned char>(adj, L.occ));              \
-    hipLaunchKernelGGL(k_chan_graphs, dim3(c.C), dim3(64), 0, s, P<const unsigned char>(adj, L.occ), c.b, c.C, \
-                       P<int>(adj, L.cgl));                                                                    \
-  } while (0)
-  if (c.prec != PREC_BF16) {
-    if (c.V == 32) PREP_ADJ(32, true);
-    else if (c.V == 64) PREP_ADJ(64, true);
-    else PREP_ADJ(128, true);
-  } else {
-    if (c.V == 32) PREP_ADJ(32, false);
-    else if (c.V == 64) PREP_ADJ(64, false);
-    else PREP_ADJ(128, false);
-  }
-#undef PREP_ADJ
+  by_v_limb(c, [&](auto v, auto f16) {
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((k_prep_adj<V, decltype(f16)::value>), grid, dim3(256), 0, s, A, c.vin, P<u16>(adj, L.Ab),
+                       P<u16>(adj, L.AbT), P<u16>(adj, L.deg));
+    stage_chan_lists<V>(c, adj, L, s);
+  });
   LAUNCHCHK();
   return GGNN_OK;
 }
@@ -1267,19 +1234,12 @@ int ggnn_forward(const ggnn_dims* d, const void* pack, const void* adj, void* ws
   if (e) return e;
   if (!pack || !adj || !ws || !h0 || !hT) return fail(GGNN_EINVAL, "forward: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
-  if (c.generic) {
-    void* adjw = const_cast<void*>(adj);  // (the channel lists are rebuilt per call)
-    switch (c.prec) {
-      case PREC_SPLIT: return gen_forward<PREC_SPLIT>(c, pack, adjw, ws, training != 0, h0, hT, s);
-      case PREC_F16: return gen_forward<PREC_F16>(c, pack, adjw, ws, training != 0, h0, hT, s);
-      default: return gen_forward<PREC_BF16>(c, pack, adjw, ws, training != 0, h0, hT, s);
-    }
-  }
-  switch (c.prec) {
-    case PREC_SPLIT: return forward_impl<PREC_SPLIT>(c, pack, adj, ws, training != 0, h0, hT, s);
-    case PREC_F16: return forward_impl<PREC_F16>(c, pack, adj, ws, training != 0, h0, hT, s);
-    default: return forward_impl<PREC_BF16>(c, pack, adj, ws, training != 0, h0, hT, s);
-  }
+  return by_prec(c.prec, [&](auto p) {
+    constexpr int PREC = decltype(p)::value;
+    // (the general path rebuilds the channel lists per call)
+    if (c.generic) return gen_forward<PREC>(c, pack, const_cast<void*>(adj), ws, training != 0, h0, hT, s);
+    return forward_impl<PREC>(c, pack, adj, ws, training != 0, h0, hT, s);
+  });
 }
 
 int ggnn_backward(const ggnn_dims* d, const void* pack, const void* adj, void* ws, const float* dhT, float* dh0,
@@ -1292,19 +1252,12 @@ int ggnn_backward(const ggnn_dims* d, const void* pack, const void* adj, void* w
   if ((c.flags & GGNN_USE_EDGE_BIAS) && !dbeta)
     return fail(GGNN_EINVAL, "backward: d_edge_biases NULL with USE_EDGE_BIAS");
   hipStream_t s = (hipStream_t)stream;
-  if (c.generic) {
-    void* adjw = const_cast<void*>(adj);
-    switch (c.prec) {
-      case PREC_SPLIT: return gen_backward<PREC_SPLIT>(c, pack, adjw, ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
-      case PREC_F16: return gen_backward<PREC_F16>(c, pack, adjw, ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
-      default: return gen_backward<PREC_BF16>(c, pack, adjw, ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
-    }
-  }
-  switch (c.prec) {
-    case PREC_SPLIT: return backward_impl<PREC_SPLIT>(c, pack, adj, ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
-    case PREC_F16: return backward_impl<PREC_F16>(c, pack, adj, ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
-    default: return backward_impl<PREC_BF16>(c, pack, adj, ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
-  }
+  return by_prec(c.prec, [&](auto p) {
+    constexpr int PREC = decltype(p)::value;
+    if (c.generic)
+      return gen_backward<PREC>(c, pack, const_cast<void*>(adj), ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
+    return backward_impl<PREC>(c, pack, adj, ws, dhT, dh0, dW, dbeta, dWg, dbg, dWc, dbc, s);
+  });
 }
 
 // ---- test / tuning hook: D[M][N] = A[M][K] B[K][N] (row-major fp32) through
@@ -1320,11 +1273,7 @@ int ggnn_dbg_gemm(const ggnn_dims* d, int M, int N, int K, const float* A, const
   a.D = D; a.sDm = N; a.sDn = 1;
   a.M = M; a.N = N; a.K = K;
   hipStream_t s = (hipStream_t)stream;
-  switch (c.prec) {
-    case PREC_SPLIT: return gg_launch<PREC_SPLIT>(a, false, true, false, K_PROP_FWD, s);
-    case PREC_F16: return gg_launch<PREC_F16>(a, false, true, false, K_PROP_FWD, s);
-    default: return gg_launch<PREC_BF16>(a, false, true, false, K_PROP_FWD, s);
-  }
+  return by_prec(c.prec, [&](auto p) { return gg_launch<decltype(p)::value>(a, false, true, false, K_PROP_FWD, s); });
 }
 
 int ggnn_dbg_gemm_ex(const ggnn_dims* d, int M, int N, int K, const void* A, int a_layout, const float* B,
@@ -1345,12 +1294,7 @@ int ggnn_dbg_gemm_ex(const ggnn_dims* d, int M, int N, int K, const void* A, int
   if (kernel >= 2 && !ring_ok(a, a16, akc, bkc)) return fail(GGNN_EINVAL, "dbg_gemm_ex: operands not ring-aligned");
   hipStream_t s = (hipStream_t)stream;
   g_gemm_force = kernel;
-  int e;
-  switch (c.prec) {
-    case PREC_SPLIT: e = gg_launch<PREC_SPLIT>(a, a16, akc, bkc, K_PROP_FWD, s); break;
-    case PREC_F16: e = gg_launch<PREC_F16>(a, a16, akc, bkc, K_PROP_FWD, s); break;
-    default: e = gg_launch<PREC_BF16>(a, a16, akc, bkc, K_PROP_FWD, s); break;
-  }
+  const int e = by_prec(c.prec, [&](auto p) { return gg_launch<decltype(p)::value>(a, a16, akc, bkc, K_PROP_FWD, s); });
   g_gemm_force = 0;
   return e;
 }

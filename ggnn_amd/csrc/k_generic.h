@@ -175,8 +175,8 @@ __global__ void k_gen_blend(const float* __restrict__ G, const float* __restrict
 // ---- backward element-wise steps, timestep t (Appendix A of SURVEY.md):
 // e1: dc = d(1-u); du = d(h-c); dzc = dc(1-c^2); dzg_u = du u(1-u);
 //     dh (second half of the [N][2H] buffer DXH) = d u
-// with the step's delta d formed on the fly (round 5: no k_gen_delta /
-// k_gen_delta0 launch in front of it): d = din[row * ldin + k] * gscale(gmax)
+// with the step's delta d formed on the fly (no staging launch in front of
+// it; k_gen_delta runs once, after step 0): d = din[row * ldin + k] * gscale(gmax)
 // through the state dropout of timestep tm (tm < 0: none) -- din = dL/dh_T
 // (ldin H, the gradient scale) at the last timestep, else the second half of
 // DXH (ldin 2H, the dh the step after left there, read before this thread
@@ -257,27 +257,6 @@ __global__ void k_gen_delta(const float* __restrict__ DXH, float* __restrict__ o
       float y = DXH[row * 2 * H + H + x.k] * osc;
       if (drop) y = drop_apply(sd, u4_get(w, u), y);
       out[row * H + x.k] = y;
-    }
-  }
-}
-// dL/dh_T staging: delta = S * dL/dh_T (gradient scale), state dropout of T-1
-__global__ void k_gen_delta0(const float* __restrict__ dhT, float* __restrict__ out, long N, int H, int v, Drop sd,
-                             int tm, const uint32_t* __restrict__ gmax) {
-  sd = drop_resolve(sd);  // (a device-resident key: loaded once)
-  const long b = N / v, total = b * ((v + 3) >> 2) * H;
-  const float sc = gscale(gmax);
-  for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
-    QuadIdx x;
-    quad_idx(q, H, v, b, x);
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    if (sd.thr) w = state_words(sd, x.g, x.i0, x.k, tm);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (u >= x.nr) break;
-      const long e = (x.row0 + u) * H + x.k;
-      float y = dhT[e] * sc;
-      if (sd.thr) y = drop_apply(sd, u4_get(w, u), y);
-      out[e] = y;
     }
   }
 }

@@ -3,47 +3,6 @@
 #pragma once
 #include "ggnn_common.h"
 
-// Pack B operand Bmat[K][N] (Bmat = S or S^T, S row-major fp32, leading dim
-// ldS) into MFMA fragment order [N/32][K/16][64][8] of 16-bit limbs (bf16, or
-// f16 for the split mode), hi part at `out`, lo part (x - limb(x)) at
-// `out + lo_off`.  blockIdx.y selects a matrix of a batch (strides sS / sO).
-// With dr.thr != 0 the source is W[c] (c = blockIdx.y) under the edge-weight
-// dropout mask of timestep t (chem_tensorflow_dense.py:397-403), applied in
-// the reference's element coordinates (i = input row, j = output column) so
-// that the forward pack (Bmat = W_c) and the backward pack (Bmat = W_c^T)
-// see the same mask.
-template <bool F16>
-__global__ void k_pack_B(const float* __restrict__ S, int ldS, long sS, int K, int N, int trans,
-                         u16* __restrict__ out, long sO, long lo_off, Drop dr, int t) {
-  dr = drop_resolve(dr);  // (a device-resident key: loaded once)
-  const int total = (N / 32) * (K / 16) * 64;
-  const float* Sb = S + sS * blockIdx.y;
-  u16* ob = out + sO * blockIdx.y;
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < total; q += gridDim.x * blockDim.x) {
-    const int lane = q & 63, fi = q >> 6;  // fragment index
-    const int nks = K / 16;
-    const int ks = fi % nks, strip = fi / nks;
-    const int n = strip * 32 + (lane & 31), k0 = ks * 16 + 8 * (lane >> 5);
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = trans ? Sb[(long)n * ldS + k0 + j] : Sb[(long)(k0 + j) * ldS + n];
-    if (dr.thr) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int wi = trans ? n : k0 + j, wj = trans ? k0 + j : n;
-        x[j] = drop_apply(dr, u4_get(edge_words(dr, blockIdx.y, wi, wj, t), wi & 3), x[j]);
-      }
-    }
-    *(uint4*)(ob + (size_t)q * 8) = pk8<F16>(x);
-    *(uint4*)(ob + lo_off + (size_t)q * 8) = pk8_lo<F16>(x);
-  }
-}
-
-__global__ void k_copy_f32(const float* __restrict__ s, float* __restrict__ d, long n) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    d[i] = s ? s[i] : 0.0f;
-}
-
 // Adjacency [b][C][vin][vin] fp32 -> per (g,c) tile:
 //   Ab  [V][V] bf16, columns permuted inside every 16-column group (8-byte
 //       chunks 1 and 2 swapped) = the k order of an accumulator-as-B operand
@@ -220,28 +179,6 @@ __global__ void __launch_bounds__(256) k_transpose(const TI* __restrict__ in, TO
       if constexpr (std::is_same<TO, float>::value) out[(long)(c0 + j) * N + r0 + i] = t[i][j];
       else out[(long)(c0 + j) * N + r0 + i] = to_limb<F16>(t[i][j]);
     }
-  }
-}
-
-// d edge_weights under edge dropout: dW[c][i][j] = sum_t mask_t(c,i,j)/keep *
-// G[t][c][i][j], G = the per-timestep h_t^T dM_{c,t} from k_wgrad.  One thread
-// per 4 consecutive rows i (one Philox draw per timestep).
-__global__ void k_edge_mask_reduce(const float* __restrict__ G, float* __restrict__ dW, int C, int H, int T, Drop dr) {
-  dr = drop_resolve(dr);  // (a device-resident key: loaded once)
-  const long total = (long)C * (H / 4) * H;
-  for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
-    const int j = q % H;
-    const int i0 = (int)((q / H) % (H / 4)) * 4;
-    const int c = (int)(q / ((long)H * (H / 4)));
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < T; ++t) {
-      const uint4 w = edge_words(dr, c, i0, j, t);
-      const float* g = G + (((long)t * C + c) * H + i0) * H + j;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] += drop_apply(dr, u4_get(w, e), g[(long)e * H]);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dW[((long)c * H + i0 + e) * H + j] = s[e];
   }
 }
 
@@ -487,8 +424,17 @@ __global__ void __launch_bounds__(64) k_chan_graphs(const unsigned char* __restr
 }
 
 // ---- all weight packs of one ggnn_pack_weights call in ONE launch: a job
-// table of k_pack_B problems (and fp32 copies for the biases); block b runs
-// job j with blk_begin[j] <= b < blk_begin[j+1]
+// table of pack problems (and fp32 copies for the biases); block b runs
+// job j with blk_begin[j] <= b < blk_begin[j+1].
+// A pack job puts the B operand Bmat[K][N] (Bmat = S or S^T, S row-major fp32,
+// leading dim ldS) into MFMA fragment order [N/32][K/16][64][8] of 16-bit
+// limbs (bf16, or f16 for the split mode), hi part at `out`, lo part
+// (x - limb(x)) at `out + lo_off`, one matrix per batch entry (strides sS /
+// sO).  With `drop` the source is W[c] (c = the batch entry) under the
+// edge-weight dropout mask of timestep t (chem_tensorflow_dense.py:397-403),
+// applied in the reference's element coordinates (i = input row, j = output
+// column) so that the forward pack (Bmat = W_c) and the backward pack
+// (Bmat = W_c^T) see the same mask.
 #define PACK_MAXJ 24
 struct PackJob {
   const float* S;

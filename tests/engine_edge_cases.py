@@ -2,8 +2,8 @@
 tests/test_gpu_engine_edges.py (GPU) and tests/test_engine_edge_inputs.py (CPU).
 
 numpy and the oracle only: nothing here touches the GPU.  The tier predicates
-restate the dispatch of ggnn_amd/csrc/ggnn_api.hip (make_cfg, fused_fwd, gru_rt,
-launch_gru_fwd, wg_plan, wgrad_lists, backward_impl) for the fp32-parity mode,
+restate the dispatch of ggnn_amd/csrc/ggnn_api.hip (make_cfg, fused_fwd, by_gru_rt,
+launch_gru_fwd, wg_plan with WgPlan::lists, backward_impl) for the fp32-parity mode,
 so the CPU module can assert that the tables reach every tier.
 """
 import functools
@@ -75,7 +75,7 @@ DENSE_CHANNEL_CASES = ["n32_c1_t1", "h256_n64", "v64", "v65_fused_b1", "fused_t1
 # graph 0 without an edge, channel 5 without an edge in any graph
 EMPTY_CASES = [
     _c("empty_n192", 3, 40, 256, 6, 2, kind="empty"),       # N % 128 != 0
-    _c("empty_lists", 2, 128, 256, 6, 2, kind="empty"),     # wgrad_lists
+    _c("empty_lists", 2, 128, 256, 6, 2, kind="empty"),     # WgPlan::lists
     _c("empty_h128", 3, 20, 128, 6, 2, kind="empty"),       # hidden 128, v -> 32: k_wgrad reads every dM^T row
 ]
 # the 16-bit modes' statistical bars need dependency-tree adjacency

@@ -11,7 +11,7 @@ below hard ones, and most of the 92 labels occur in a handful of sentences.
 The backward runs on S * dL/dh_T with ONE power of two S for the batch
 (ggnn_common.h gscale), sums every graph into one tile per channel (k_wgrad,
 the general path's split-K slabs) and decides per graph and per channel what to
-compute at all (wgrad_lists, the pair rows, empty-channel skipping).  uneven()
+compute at all (WgPlan::lists, the pair rows, empty-channel skipping).  uneven()
 builds batches of that kind and slice_errors() measures every graph's dL/dh0
 and every channel's dW_c / dbeta_c against its OWN maximum.
 """
@@ -57,7 +57,7 @@ CASES = [
     # b = 4 rather than 2: the target-less graph 1 and the two rare channels'
     # graphs 2 and 3 stay distinct (N = 512, still a fraction of a second).
     # seed 0: 6.3e-4 and 0.034 / 0.043; 1: 0.018 / 0.022; 2: 0.052 / 0.082
-    _c("u256_v128", 4, 128, 256, 4, 2, seed=3),                # config 3's tile shape: fused forward, wgrad_lists
+    _c("u256_v128", 4, 128, 256, 4, 2, seed=3),                # config 3's tile shape: fused forward, WgPlan::lists
     # seed 0: dbeta share 0.017
     _c("u128_drop", 8, 32, 128, 6, 2, ek=0.9, sk=0.9, seed=1),  # dropout masks on a rare channel
     _c("u256_lossscale", 4, 40, 256, 6, 3, seed=5, lscale=2.0 ** -14),  # u256_pad's data under another S

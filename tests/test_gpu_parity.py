@@ -865,7 +865,7 @@ def test_fused_forward_16bit_matches_unfused(precision):
 
 @pytest.mark.parametrize("b,v,h,C,T,keep,precision", [
     (8, 128, 256, 8, 3, 1.0, "fp32"),     # k_wgrad256 (256 x 256 tiles), graph-listed dW_c
-    (8, 128, 256, 8, 3, 0.9, "fp32"),     # edge dropout: per-timestep dW tiles, k_edge_mask_reduce
+    (8, 128, 256, 8, 3, 0.9, "fp32"),     # edge dropout: timestep-aligned dW chunks, masked in k_wgrad_reduce
     (3, 64, 256, 4, 2, 0.9, "fp32"),      # N % 128 != 0 at hidden 256: k_wgrad (128 x 128 tiles)
     (6, 64, 128, 4, 3, 1.0, "fp32"),      # hidden 128: k_wgrad
     (8, 128, 256, 8, 2, 1.0, "bf16"),

@@ -7,9 +7,8 @@ dL/dh0.
 
 Cases: every padded graph size V in {32, 64, 128} at hidden {64, 128, 256} in
 the fp32-parity mode, and fp16 / bf16 at (128, 256); b = 3, C = 4, T = 2.
-(Hidden 64 runs the general path: the dispatcher's hidden-64 branch of the
-specialised kernels is not reached by any hidden size the ABI accepts; the
-case stays so that a change of that rule is covered.)  Graph 0 has no edge in
+(Hidden 64 runs the general path: the specialised kernels exist for hidden
+128 / 256 only; the case stays so that a change of that rule is covered.)  Graph 0 has no edge in
 channel 3 (its dbeta partials and, where the weight gradient reads every row,
 its dM^T rows are zero-filled), graph 1 has a single edge (three empty
 channels), graph 2's dL/dh_T is scaled by 2^-6.  Every buffer the step writes

@@ -241,7 +241,7 @@ def test_case_table_reaches_its_tiers():
             (64, False, True, True, "k_gru_fwd2", 2)
     x = t["u256_n320"]      # N % 128 != 0 at hidden 256: the 128-tile k_wgrad, every dM^T row
     assert x["N"] % 128 != 0 and (x["V"], x["big"], x["lists"], x["gru_fwd"]) == (64, False, False, "k_gru_fwd<256,2>")
-    x = t["u256_v128"]      # config 3's tile shape: fused forward, wgrad_lists, four K chunks
+    x = t["u256_v128"]      # config 3's tile shape: fused forward, WgPlan::lists, four K chunks
     assert (x["V"], x["fused"], x["big"], x["lists"], x["nchunks"]) == (128, True, True, True, 4)
     x = t["u128_drop"]      # edge dropout: timestep-aligned dW chunks; state dropout outside the fused forward
     assert x["cpt"] == 1 and not x["in_place"] and SC.ALL["u128_drop"].sk < 1.0
