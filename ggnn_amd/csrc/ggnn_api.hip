@@ -31,6 +31,7 @@
 #include "k_generic.h"
 #include "k_pairs.h"
 #include "k_tree_sample.h"
+#include "k_proj_sample.h"
 
 // ---------------------------------------------------------------------------
 // error handling (thread-local last error; no exception crosses the ABI)
@@ -1931,6 +1932,41 @@ int ggnn_tree_sample(const ggnn_dims* d, const float* probs_head, int32_t o, con
                      (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (const int*)marg_status,
                      (int)num_samples, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob,
                      (int*)status, need ? (float*)workspace : nullptr, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+
+// projective dependency trees drawn from the distribution of
+// ggnn_projective_marginals (k_proj_sample.h); booked under the heads kind
+static_assert(GGNN_PROJ_SAMPLE_LDS_MAXN == PROJ_SAMPLE_LDS_MAXN && GGNN_PROJ_SAMPLE_CHUNK == PROJ_SAMPLE_CHUNK,
+              "projective sample constants");
+static size_t proj_sample_chunks(int32_t num_samples) {
+  return ((size_t)num_samples + GGNN_PROJ_SAMPLE_CHUNK - 1) / GGNN_PROJ_SAMPLE_CHUNK;
+}
+size_t ggnn_projective_sample_workspace_bytes(int32_t b, int32_t v, int32_t num_samples) {
+  if (b < 1 || num_samples < 1 || v <= GGNN_PROJ_SAMPLE_LDS_MAXN) return 0;
+  return (size_t)b * proj_sample_chunks(num_samples) * 8 * (size_t)v * ((size_t)v + 1);
+}
+int ggnn_projective_sample(const ggnn_dims* d, const float* probs_head, int32_t o, const int32_t* n_nodes,
+                           int32_t single_root, int32_t num_samples, uint64_t seed, int32_t* heads, float* log_prob,
+                           int32_t* status, float* logz, void* workspace, size_t workspace_bytes,
+                           ggnn_stream_t stream) {
+  const char* const name = "projective_sample";
+  const bool null_arg = !probs_head || !n_nodes || !heads || !log_prob || !status;
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
+  if (num_samples < 1 || num_samples > GGNN_SAMPLE_MAX)
+    return fail(GGNN_EINVAL, "projective_sample: num_samples must lie in 1.." + std::to_string(GGNN_SAMPLE_MAX) +
+                                 " (got " + std::to_string(num_samples) + ")");
+  const long chunks = (long)proj_sample_chunks(num_samples);
+  if ((long)d->b * chunks > 0x7FFFFFFFL) return fail(GGNN_EINVAL, "projective_sample: b * chunks exceeds the grid");
+  const size_t need = ggnn_projective_sample_workspace_bytes(d->b, d->v, num_samples);
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_projective_sample<PROJ_SAMPLE_CHUNK>, dim3((unsigned)(d->b * chunks)), dim3(256), 0, s, probs_head, (int)o,
+                     (const int*)n_nodes, (int)d->v, (int)single_root, (int)num_samples, (int)chunks,
+                     (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob, (int*)status, logz,
+                     need ? (float*)workspace : nullptr, (long)4 * PROJ_TRI((long)d->v));
   LAUNCHCHK();
   return GGNN_OK;
 }

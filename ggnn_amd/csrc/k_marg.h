@@ -100,22 +100,39 @@ DEV void marg_store(float* __restrict__ marg, int* __restrict__ scores, long at,
   if (scores) scores[at] = (int)rintf(val * MARG_SCALE);
 }
 
-// The passes of one graph (tab: MARG_TABLES * PROJ_TRI(m) floats, LDS or
-// global; marg / scores / logz point at the graph's own outputs).  Returns 1
-// with the outputs written, 2 (nothing written) when ln Z is not finite.
-// Called by the whole workgroup.
-DEV int marg_solve(float* tab, const float* __restrict__ P, int o, int v, int n, int m, int lo, int single_root,
-                   float* crow, float* zs, float* __restrict__ marg, int* __restrict__ scores,
-                   float* __restrict__ logz, int tid) {
+// c[i] of one graph (n >= 2): the largest allowed ln p of every word's row, a
+// wave per row.  Returns whether a word has no allowed arc (the same for every
+// thread).  Called by the whole workgroup; ends in a barrier.
+DEV bool marg_crow(const float* __restrict__ P, int o, int n, float* crow, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  bool empty = false;
+  for (int i = 1 + wave; i < n; i += 4) {
+    float mx = 0.f;
+    for (int j = lane; j < n; j += 64) {
+      const float p = P[(long)i * o + j];
+      if (j != i && marg_allowed(p)) mx = fmaxf(mx, p);
+    }
+    for (int w = 32; w >= 1; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w));
+    if (lane == 0) crow[i] = mx > 0.f ? logf(mx) : 0.f;
+    empty |= !(mx > 0.f);
+  }
+  if (tid == 0) crow[0] = 0.f;
+  return __syncthreads_or(empty);
+}
+
+// The inside passes of one graph (tab: the four inside tables first, 4 *
+// PROJ_TRI(m) floats, LDS or global).  Returns 1 with the tables filled on the
+// shifted potentials (crow updated), zs[0] = their ln Z'' and zs[1] = ln Z of
+// the graph's own potentials, 2 when ln Z is not finite.  Called by the whole
+// workgroup; ends in a barrier.  Shared with k_proj_sample.h.
+DEV int marg_inside(float* tab, const float* __restrict__ P, int o, int n, int m, int lo, int single_root,
+                    float* crow, float* zs, int tid) {
   const int lane = tid & 63, wave = tid >> 6;
   const int tri = PROJ_TRI(m);
   float* CR = tab;
   float* CL = tab + tri;
   float* IR = tab + 2 * tri;
   float* IL = tab + 3 * tri;
-  float* OR = tab + 4 * tri;
-  float* OL = tab + 5 * tri;
-  float* OB = tab + 6 * tri;
   // ---- inside, twice: the first pass finds ln Z' on psi = ln p - (the row's largest ln p); the second runs
   // on psi - ln Z' / (n - 1), every word giving up its share of ln Z', so that a span's value stays near 0
   // instead of growing with its length, where fp32 is coarse (ln Z'' is then about 0)
@@ -184,6 +201,27 @@ DEV int marg_solve(float* tab, const float* __restrict__ P, int o, int v, int n,
   }
   __syncthreads();
   if (!(fabsf(zs[1]) <= FLT_MAX)) return 2;
+  return 1;
+}
+
+// The passes of one graph (tab: MARG_TABLES * PROJ_TRI(m) floats, LDS or
+// global; marg / scores / logz point at the graph's own outputs).  Returns 1
+// with the outputs written, 2 (nothing written) when ln Z is not finite.
+// Called by the whole workgroup.
+DEV int marg_solve(float* tab, const float* __restrict__ P, int o, int v, int n, int m, int lo, int single_root,
+                   float* crow, float* zs, float* __restrict__ marg, int* __restrict__ scores,
+                   float* __restrict__ logz, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int tri = PROJ_TRI(m);
+  float* CR = tab;
+  float* CL = tab + tri;
+  float* IR = tab + 2 * tri;
+  float* IL = tab + 3 * tri;
+  float* OR = tab + 4 * tri;
+  float* OL = tab + 5 * tri;
+  float* OB = tab + 6 * tri;
+  if (marg_inside(tab, P, o, n, m, lo, single_root, crow, zs, tid) != 1) return 2;
+  const float z = zs[0];
   if (tid == 0) *logz = zs[1];
   // ---- every arc starts as "not allowed"; the allowed ones are written once each below
   for (long x = tid; x < (long)v * o; x += 256) {
@@ -264,7 +302,7 @@ __global__ void __launch_bounds__(256) k_projective_marginals(const float* __res
                                                               int single_root, float* __restrict__ marg,
                                                               float* __restrict__ logz, int* __restrict__ scores,
                                                               int* __restrict__ status, float* ws, long ws_stride) {
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x, tid = threadIdx.x;
   const int n = tree_node_count(n_nodes[g], v, o);
   const long base = (long)g * v * o;
   const float* __restrict__ P = probs + base;
@@ -273,20 +311,7 @@ __global__ void __launch_bounds__(256) k_projective_marginals(const float* __res
 
   int st = 0;
   if (n >= 2) {
-    // ---- c[i]: the largest allowed ln p of every word's row (a wave per row)
-    bool empty = false;
-    for (int i = 1 + wave; i < n; i += 4) {
-      float mx = 0.f;
-      for (int j = lane; j < n; j += 64) {
-        const float p = P[(long)i * o + j];
-        if (j != i && marg_allowed(p)) mx = fmaxf(mx, p);
-      }
-      for (int w = 32; w >= 1; w >>= 1) mx = fmaxf(mx, __shfl_xor(mx, w));
-      if (lane == 0) crow[i] = mx > 0.f ? logf(mx) : 0.f;
-      empty |= !(mx > 0.f);
-    }
-    if (tid == 0) crow[0] = 0.f;
-    if (__syncthreads_or(empty)) {
+    if (marg_crow(P, o, n, crow, tid)) {
       st = 2;  // a word without an allowed arc
     } else {
       const int lo = single_root ? 1 : 0, m = n - lo;

@@ -1,8 +1,8 @@
 """Decoding: the chain decode -> marginals -> tree / projective pass ->
 confidences -> samples, written once against a backend with the device
-binding's seven methods (``decode``, ``tree_decode``, ``projective_decode``,
+binding's eight methods (``decode``, ``tree_decode``, ``projective_decode``,
 ``projective_marginals``, ``tree_marginals``, ``arc_confidence``,
-``tree_sample``):
+``tree_sample``, ``projective_sample``):
 heads.OutputHeads on the GPU, ``HostDecoder`` over evaluation.*_arrays for a
 model on a CPU device; and the model's decoding entries (``DecodingMixin``)."""
 from __future__ import annotations
@@ -25,6 +25,15 @@ _NO_CONFIDENCE = {      # the projective confidence with tree=True / "mbr", in e
     "parse": "parse: confidence needs tree=False, \"projective\" or \"projective-mbr\", or "
              "confidence=\"nonprojective\""}
 _MBR_FAMILY = {"projective-mbr": "projective", "mbr": "nonprojective"}     # the marginals an MBR mode is built on
+SAMPLE_FAMILIES = ("nonprojective", "projective")                          # the distributions samples are drawn from
+
+
+def _sample_family(family):
+    """The ``sample_family`` / ``family`` keyword: "nonprojective" (all
+    dependency trees) or "projective"; anything else is a ValueError."""
+    if isinstance(family, str) and family in SAMPLE_FAMILIES:
+        return family
+    raise ValueError('sample_family must be "nonprojective" or "projective", got %r' % (family,))
 
 
 def _confidence_mode(confidence):
@@ -72,7 +81,7 @@ def _in_place(host_form):
 
 
 class HostDecoder:
-    """OutputHeads' seven decoding methods over the host forms, numpy in and
+    """OutputHeads' eight decoding methods over the host forms, numpy in and
     out; the marginals as float32, without the host forms' span_max / cond /
     margin."""
     tree_decode = _in_place(_eval.tree_decode_arrays)
@@ -99,6 +108,14 @@ class HostDecoder:
         heads, log_prob, status, _ = _eval.tree_sample_arrays(probs_head, n_nodes, num_samples, seed, single_root)
         return heads, log_prob.astype(np.float32), status
 
+    def projective_sample(self, probs_head, n_nodes, num_samples, seed=0, single_root=True):
+        """(heads int32 [b, K, v], log_prob float32 [b, K], status int32
+        [b, K], logz float32 [b]) of evaluation.projective_sample_arrays
+        (float64)."""
+        heads, log_prob, status, _, logz = _eval.projective_sample_arrays(probs_head, n_nodes, num_samples, seed,
+                                                                          single_root)
+        return heads, log_prob.astype(np.float32), status, logz.astype(np.float32)
+
 
 def _select(keep, x, fill):
     """x where keep, ``fill`` elsewhere: int32, in x's own array type."""
@@ -108,7 +125,7 @@ def _select(keep, x, fill):
 
 
 def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=True, confidence=False, samples=0,
-                 sample_seed=0):
+                 sample_seed=0, sample_family="nonprojective"):
     """The decode and what follows it, in launch order and in ``backend``'s
     array type (probs [b, v, o], probs_e [b, v, oe] float32, n_nodes int32
     [b], labels: the two heads' targets or None).  mode True / "projective":
@@ -123,7 +140,10 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     the distribution over all dependency trees (backend.tree_sample on n *
     regular, with the "mbr" marginals where the chain has them) as
     sampled_heads [b, K, v], sample_log_prob [b, K], sample_status [b, K] (2
-    where a graph is not regular)."""
+    where a graph is not regular); sample_family="projective" draws them from
+    the distribution over projective trees instead (backend.projective_sample
+    on n * regular, which needs no marginals)."""
+    sample_family = _sample_family(sample_family)
     on_device, family, confidence = isinstance(probs, torch.Tensor), _MBR_FAMILY.get(mode), _confidence_mode(confidence)
     marginals = lambda kind: backend.projective_marginals if kind == "projective" else backend.tree_marginals
     pred, gold, counts = backend.decode([probs, probs_e], n_nodes, labels)
@@ -144,9 +164,12 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
         if family != confidence:     # (nothing reads the integer scores)
             marg, logz, _, _ = marginals(confidence)(probs, n_reg, single_root, with_scores=False)
         out["head_confidence"], out["log_partition"] = backend.arc_confidence(marg, n_nodes, pred), logz
-    if samples:
+    if samples and sample_family == "projective":
+        heads, log_prob, status, _ = backend.projective_sample(probs, n_reg, samples, sample_seed, single_root)
+    elif samples:
         have = (marg, logz, scores, has_marg) if family == "nonprojective" else None
         heads, log_prob, status = backend.tree_sample(probs, n_reg, samples, sample_seed, single_root, have)
+    if samples:
         out["sampled_heads"], out["sample_log_prob"] = heads, log_prob
         out["sample_status"] = _select(counts[:, 4:5] == 1, status, 2)
     return out
@@ -187,7 +210,7 @@ class DecodingMixin:
         return loss
 
     def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False, samples=0,
-                        sample_seed=0):
+                        sample_seed=0, sample_family="nonprojective"):
         """_eval_forward of a feed (default: the staged one), then decode_chain
         eagerly on the same stream (never inside a captured step).  Returns a
         dict: loss (scalar tensor), ph (the staged placeholders), b, v, n_nodes
@@ -215,7 +238,7 @@ class DecodingMixin:
             labels = [np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o),
                       np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)] if with_gold else None
         r.update(decode_chain(backend, probs, probs_e, n, labels if with_gold else None, mode, single_root, confidence,
-                              samples, sample_seed))
+                              samples, sample_seed, sample_family))
         return r
 
     def _host_pred(self, ph, b, v):
@@ -227,7 +250,8 @@ class DecodingMixin:
                                      np.asarray(ph["node_mask"], np.float32).reshape(b, v, o),
                                      np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
 
-    def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False, samples=0, sample_seed=0):
+    def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False, samples=0, sample_seed=0,
+                      sample_family="nonprojective"):
         """The predicted tree of every graph of a batch: {'heads': [b, v],
         'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
         arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
@@ -273,12 +297,19 @@ class DecodingMixin:
         probability (-inf where the status is not 1); 'sample_status' [b, K]
         int32: 1 = drawn, 0 = fewer than two nodes, 2 = no tree exists, a
         numerical dead end or not attempted (an irregular graph, a feed whose
-        masks are not in closed form).  samples = 0 launches nothing."""
+        masks are not in closed form).  samples = 0 launches nothing.
+        sample_family="projective": the samples are drawn from the
+        distribution over PROJECTIVE trees instead (ggnn_projective_sample: the
+        distribution of tree="projective-mbr", confidence="projective" and
+        structured_loss="projective"; every returned tree is projective and
+        'sample_log_prob' is normalised by that distribution's Z); the keys and
+        their shapes are the same.  Any other value is a ValueError."""
         tree = _tree_mode(tree, confidence, "predict_batch")
+        sample_family = _sample_family(sample_family)
         samples = int(samples)
         if not 0 <= samples <= _eval.SAMPLE_MAX:
             raise ValueError("samples must lie in 0..%d (got %d)" % (_eval.SAMPLE_MAX, samples))
-        r = self._decode_forward(feed_dict, False, tree, single_root, confidence, samples, sample_seed)
+        r = self._decode_forward(feed_dict, False, tree, single_root, confidence, samples, sample_seed, sample_family)
         ph, b, v, pred = r["ph"], r["b"], r["v"], r["pred"]
         if pred is None:
             pred = self._host_pred(ph, b, v)
@@ -305,7 +336,7 @@ class DecodingMixin:
                 out[k] = _as_np(r[k])
         return out
 
-    def sample_trees(self, raw_data, num_samples, single_root=True, seed=0):
+    def sample_trees(self, raw_data, num_samples, single_root=True, seed=0, family="nonprojective"):
         """Dependency trees of raw btb sentences (parse's input) drawn from the
         distribution over all dependency trees that the head probabilities
         define (predict_batch(samples=num_samples)).  Returns (trees,
@@ -316,13 +347,15 @@ class DecodingMixin:
         sample whose status is not 1 is left out; a sentence
         process_raw_graphs drops yields [].  Batch number i of the iterator
         draws with seed (seed + i) mod 2^64: the same call gives the same
-        trees."""
+        trees.  family="projective": the trees are drawn from the distribution
+        over projective trees (predict_batch(sample_family="projective"))."""
+        family = _sample_family(family)
         raw = [{"targets": [], **d, "id": k} for k, d in enumerate(raw_data)]
         out, log_probs = [[] for _ in raw], [[] for _ in raw]
         data = self.process_raw_graphs(raw, False)
         for i, feed in enumerate(self.make_minibatch_iterator(data, False)):
             p = self.predict_batch(feed, False, single_root, samples=num_samples,
-                                   sample_seed=(int(seed) + i) % 2 ** 64)
+                                   sample_seed=(int(seed) + i) % 2 ** 64, sample_family=family)
             for g, k in enumerate(p["sentences_id"]):
                 n = int(p["n_nodes"][g])
                 for s in np.nonzero(p["sample_status"][g] == 1)[0]:

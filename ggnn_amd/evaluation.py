@@ -701,10 +701,12 @@ def _arc_log_potentials(p, n, dtype):
         return np.where(ok, np.log(np.where(ok, q, 1)), -np.inf).astype(dtype), ok
 
 
-def _inside_outside(psi, n, single_root):
-    """One graph: psi [n, n] log potentials (-inf = not allowed).  Returns
-    (logz, marg [n, n] in psi's dtype, the largest absolute finite table
-    value, ln Z included); logz = -inf when no projective tree exists."""
+def _inside(psi, n, single_root):
+    """One graph's inside pass: psi [n, n] log potentials (-inf = not
+    allowed).  Returns (the tables [CR, CL, IR, IL] with T[d, s] the span
+    s..s+d over the positions 0..m-1 = the nodes lo..n-1, logz, w, root): w the
+    positions' own potentials, root [m] those of ROOT's arcs (None without
+    single_root); logz = -inf when no projective tree exists."""
     dt = psi.dtype
     lo = 1 if single_root else 0
     m = n - lo
@@ -726,7 +728,20 @@ def _inside_outside(psi, n, single_root):
         logz = _lse(CL[p, 0] + CR[m - 1 - p, p] + root)
     else:
         logz = CR[m - 1, 0]
-    tables = [CR, CL, IR, IL]
+    return [CR, CL, IR, IL], logz, w, root
+
+
+def _inside_outside(psi, n, single_root):
+    """One graph: psi [n, n] log potentials (-inf = not allowed).  Returns
+    (logz, marg [n, n] in psi's dtype, the largest absolute finite table
+    value, ln Z included); logz = -inf when no projective tree exists."""
+    dt = psi.dtype
+    lo = 1 if single_root else 0
+    m = n - lo
+    tables, logz, w, root = _inside(psi, n, single_root)
+    CR, CL, IR, IL = tables
+    neg = lambda: np.full((m, m), -np.inf, dt)
+    p = np.arange(m)
     marg = np.zeros((n, n), dt)
     if not np.isfinite(logz):
         return dt.type(-np.inf), marg, 0.0
@@ -1250,3 +1265,178 @@ def tree_sample_arrays(probs_head, n_nodes, num_samples, seed, single_root=True,
                 heads[g, s, 1:n] = out[1:]
                 log_prob[g, s] = float(np.sum(ln_p[np.arange(1, n), out[1:]])) - float(logz[g])
     return heads, log_prob, status, margin
+
+
+# ------------------------------------------------ sampling projective trees
+# Host form of ``ggnn_projective_sample`` (include/ggnn.h,
+# csrc/k_proj_sample.h): a top-down walk over _inside's tables.  An item (kind,
+# s, t) stands for one table entry and is expanded by one draw over its terms,
+# in ascending r:
+#   0  ROOT's child (single_root)   r = 0..m-1   CL[0][r] + CR[r][m-1] + psi(r+1 takes ROOT)
+#   1  CR[s][t], s < t              r = s+1..t   IR[s][r] + CR[r][t]
+#   2  CL[s][t], s < t              r = s..t-1   CL[s][r] + IL[r][t]
+#   3  IR[s][t]  (t takes s)        r = s..t-1   CR[s][r] + CL[r+1][t]
+#   4  IL[s][t]  (s takes t)        as kind 3
+# with masses exp(term - largest term); the chosen term's two entries are the
+# item's children (a complete span s = t is a leaf).  Every projective tree has
+# exactly one derivation, and the product of its draws' probabilities is its
+# weight / Z.
+PROJ_SAMPLE_LDS_MAXN = 128     # GGNN_PROJ_SAMPLE_LDS_MAXN
+PROJ_SAMPLE_CHUNK = 16         # GGNN_PROJ_SAMPLE_CHUNK
+PROJ_SAMPLE_STREAM = 0x50000000    # the last Philox counter word of every draw
+
+
+def projective_sample_uniform(seed, g, s, kind, a, t):
+    """The uniform of item (kind, a, t)'s draw in sample s of graph g: the top
+    24 bits of Philox word x at counter (kind << 16 | a << 8 | t, s, g,
+    0x50000000) under the 64-bit seed as key, times 2^-24."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    x = philox4x32_10((kind << 16 | a << 8 | t, s, g, PROJ_SAMPLE_STREAM), (seed & 0xFFFFFFFF, seed >> 32))[0]
+    return (x >> 8) * 2.0 ** -24
+
+
+def _forced_split(kind, s, t, hp, m):
+    """The r that the derivation of the heads hp (by position, -1: ROOT or
+    none) takes at item (kind, s, t); -1 when there is none."""
+    def under(d, x):                                    # d is x or a descendant of x
+        for _ in range(m + 1):
+            if d == x:
+                return True
+            if not 0 <= d < m:
+                return False
+            d = hp[d]
+        return False
+    if kind == 1:
+        return max([d for d in range(s + 1, t + 1) if hp[d] == s], default=-1)
+    if kind == 2:
+        return min([d for d in range(s, t) if hp[d] == t], default=-1)
+    if kind == 3:
+        return min(d for d in range(s + 1, t + 1) if under(d, t)) - 1
+    return max(d for d in range(s, t) if under(d, s))
+
+
+def _projective_walk(tables, root, m, lo, dt, uniform, f):
+    """One sample: (heads by node [lo + m] or None on a dead end, the sum of
+    the logs of the draws' probabilities, margin).  f: heads by node to
+    follow, or None."""
+    CR, CL, IR, IL = tables
+    out = np.full(lo + m, -1, np.int64)
+    hp = None
+    if f is not None:                                   # by position; ROOT (single_root) and junk: -1
+        hp = [int(f[lo + d]) - lo if lo <= f[lo + d] < lo + m else -1 for d in range(m)]
+    stack = [(0, 0, 0)] if lo else ([(1, 0, m - 1)] if m > 1 else [])
+    lp, mar = 0.0, np.inf
+    while stack:
+        kind, s, t = stack.pop()
+        if kind == 0:
+            r = np.arange(m)
+            terms = CL[r, 0] + CR[m - 1 - r, r] + root
+        elif kind == 1:
+            r = np.arange(s + 1, t + 1)
+            terms = IR[r - s, s] + CR[t - r, r]
+        elif kind == 2:
+            r = np.arange(s, t)
+            terms = CL[r - s, s] + IL[t - r, r]
+        else:
+            r = np.arange(s, t)
+            terms = CR[r - s, s] + CL[t - r - 1, r + 1]
+        top = terms.max()
+        if top == -np.inf:
+            return None, lp, mar
+        q = np.where(terms == -np.inf, 0, np.exp(terms - top)).astype(dt)
+        want = None
+        if f is not None:
+            if kind == 0:
+                took = [d for d in range(m) if f[lo + d] == 0]
+                want = took[0] if len(took) == 1 else -1
+            else:
+                want = _forced_split(kind, s, t, hp, m) - int(r[0])
+        j, pr, mr = _sample_pick(q, uniform(kind, s, t), dt, want)
+        if j < 0:
+            return None, lp, mar
+        mar = min(mar, mr)
+        if not pr > 0:                                  # (forced only)
+            return out, -np.inf, mar
+        lp += np.log(pr)
+        r = int(r[j])
+        if kind == 0:
+            out[lo + r] = 0
+            kids = [(2, 0, r), (1, r, m - 1)]
+        elif kind == 1:
+            kids = [(3, s, r), (1, r, t)]
+        elif kind == 2:
+            kids = [(2, s, r), (4, r, t)]
+        else:
+            if kind == 3:
+                out[lo + t] = lo + s
+            else:
+                out[lo + s] = lo + t
+            kids = [(1, s, r), (2, r + 1, t)]
+        stack += [k for k in kids if k[1] < k[2]]
+    return out, lp, mar
+
+
+def projective_sample_arrays(probs_head, n_nodes, num_samples, seed, single_root=True, dtype=np.float64, forced=None):
+    """The host form of ``ggnn_projective_sample`` (include/ggnn.h):
+    num_samples projective dependency trees per graph, drawn from the
+    distribution that projective_marginals_arrays(probs_head, n_nodes,
+    single_root) describes.  Returns (heads int32 [b, K, v], log_prob [b, K],
+    status int32 [b, K], margin float64 [b, K], logz [b]).  heads, log_prob and
+    margin: as tree_sample_arrays'.  status: 1 drawn, 0 n < 2, 2 no projective
+    tree or a dead end (a draw whose masses do not sum to > 0).  logz: as
+    projective_marginals_arrays'.  Sample s of graph g depends on (seed, g, s)
+    alone.  ``forced``: heads [b, v] or [b, K, v] to follow in place of the
+    draws; log_prob is then the sum of the logs of the conditional
+    probabilities met (-inf for a head vector that is no projective tree of
+    the distribution) and heads returns them.  Tables in ``dtype``."""
+    p = np.asarray(probs_head, np.float32)
+    if p.ndim != 3:
+        raise ValueError("probs_head must be [b, v, o]")
+    b, v, o = p.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("projective sampling needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    K = int(num_samples)
+    if not 1 <= K <= SAMPLE_MAX:
+        raise ValueError("num_samples must lie in 1..%d (got %d)" % (SAMPLE_MAX, K))
+    dt = np.dtype(dtype)
+    single_root = bool(single_root)
+    lo = 1 if single_root else 0
+    nn = _node_counts(n_nodes, b, v, o)
+    if forced is not None:
+        forced = np.asarray(forced, np.int64)
+        if forced.ndim == 2:
+            forced = np.repeat(forced[:, None, :], K, axis=1)
+        if forced.shape != (b, K, v):
+            raise ValueError("forced must be [b, v] or [b, num_samples, v]")
+    heads = np.full((b, K, v), -1, np.int32)
+    log_prob = np.full((b, K), -np.inf, np.float64)
+    status = np.zeros((b, K), np.int32)
+    margin = np.full((b, K), np.inf, np.float64)
+    logz = np.zeros(b, dt)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2:
+            continue
+        psi, ok = _arc_log_potentials(p[g], n, dt)
+        tables, lz, _, root = _inside(psi, n, single_root)
+        logz[g] = lz
+        if not np.isfinite(lz):
+            status[g] = 2
+            continue
+        ln_p = np.log(np.where(ok, p[g, :n, :n], 1).astype(np.float64))
+        for s in range(K):
+            f = None if forced is None else forced[g, s]
+            out, lp, mar = _projective_walk(tables, root, n - lo, lo, dt,
+                                            lambda kind, a, t: projective_sample_uniform(seed, g, s, kind, a, t), f)
+            if out is None:
+                status[g, s] = 2
+                continue
+            status[g, s] = 1
+            margin[g, s] = mar
+            if f is not None:
+                heads[g, s, 1:n] = f[1:n]
+                log_prob[g, s] = lp if np.array_equal(out[1:], f[1:n]) else -np.inf
+            else:
+                heads[g, s, 1:n] = out[1:]
+                log_prob[g, s] = float(np.sum(ln_p[np.arange(1, n), out[1:]])) - float(lz)
+    return heads, log_prob, status, margin, logz

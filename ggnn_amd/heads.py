@@ -179,6 +179,7 @@ class OutputHeads:
         self._marg_ws = None   # ggnn_projective_marginals' workspace (graphs above MARG_LDS_MAXN nodes)
         self._lapl_ws = None   # ggnn_tree_marginals' workspace (graphs above LAPL_LDS_MAXN nodes)
         self._sample_ws = None  # ggnn_tree_sample's workspace (graphs above SAMPLE_LDS_MAXN nodes)
+        self._proj_sample_ws = None  # ggnn_projective_sample's workspace (graphs above PROJ_SAMPLE_LDS_MAXN nodes)
         self._loss_ws = None   # ggnn_tree_loss' workspace (n_eff, then the family's marginals workspace)
         self._saved = None
         # the last forward's structured loss (tree_loss=): the marginals that
@@ -499,6 +500,45 @@ class OutputHeads:
                                               0 if workspace is None else workspace.numel(), _stream()),
                    "ggnn_tree_sample")
         return heads, log_prob, status
+
+    def projective_sample(self, probs_head, n_nodes, num_samples, seed=0, single_root=True, workspace=None):
+        """num_samples projective dependency trees per graph drawn from the
+        distribution over projective trees that the head probabilities define
+        (``projective_marginals``' distribution), on the current stream
+        (ggnn_projective_sample: one inside pass per graph, a top-down walk
+        over its tables per sample; no marginals are needed).  probs_head:
+        float32 [b, v, o]; n_nodes: int32 [b]; seed: a 64-bit integer (sample s
+        of graph g depends on seed, g and s alone).  Returns (heads int32
+        [b, K, v]: the head of word i, -1 on row 0, the rows >= n and where
+        status != 1; log_prob float32 [b, K]: ln of the tree's probability,
+        -inf where status != 1; status int32 [b, K]: 1 = drawn, 0 = n < 2, 2 =
+        no projective tree exists or a numerical dead end; logz float32 [b]:
+        ``projective_marginals``' ln Z).  workspace: a uint8 tensor to use
+        instead of the binding's own (grown on demand; needed for v >
+        PROJ_SAMPLE_LDS_MAXN only)."""
+        p = probs_head
+        _check_tensor(p, "probs_head", torch.float32)
+        b, v, o = p.shape
+        dev = p.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("projective_sample needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
+        K = int(num_samples)
+        if not 1 <= K <= _lib.SAMPLE_MAX:
+            raise ValueError("num_samples must lie in 1..%d (got %d)" % (_lib.SAMPLE_MAX, K))
+        _check_n_nodes(n_nodes, b, dev)
+        need = int(self._lib.ggnn_projective_sample_workspace_bytes(b, v, K))
+        workspace = self._workspace("_proj_sample_ws", need, dev, workspace)
+        heads = torch.empty(b, K, v, dtype=torch.int32, device=dev)
+        log_prob = torch.empty(b, K, dtype=torch.float32, device=dev)
+        status = torch.empty(b, K, dtype=torch.int32, device=dev)
+        logz = torch.empty(b, dtype=torch.float32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_projective_sample(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes), int(bool(single_root)),
+                                                    K, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(heads), _ptr(log_prob),
+                                                    _ptr(status), _ptr(logz), _ptr(workspace),
+                                                    0 if workspace is None else workspace.numel(), _stream()),
+                   "ggnn_projective_sample")
+        return heads, log_prob, status, logz
 
     def arc_confidence(self, marg, n_nodes, pred):
         """conf float32 [b, v]: marg[g, i, pred[g, i, 0]], 0 where there is no

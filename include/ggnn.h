@@ -733,6 +733,74 @@ int ggnn_tree_sample(const ggnn_dims* d,           /* b, v used */
                      int32_t* status,              /* device [b][K] out */
                      void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* Projective dependency trees drawn from the distribution that
+ * ggnn_projective_marginals describes (weight of a tree: the product of its
+ * words' head probabilities, over the trees without crossing arcs, ROOT
+ * leftmost; single_root: exactly one ROOT child): num_samples = K trees per
+ * graph.  Self-contained: no prior marginals call is needed.  Potentials,
+ * allowed arcs, the clamping of n, the positions p = 0..m-1, the tables CR, CL,
+ * IR, IL, their two inside passes and ln Z are ggnn_projective_marginals'.  One
+ * inside pass serves every sample of a graph; a sample expands items top-down.
+ * An item (kind, s, t) stands for one table entry; its terms, in ascending r:
+ *   0  ROOT's child (single_root; s = t = 0)
+ *                      r = 0..m-1: CL[0][r] + CR[r][m-1] + psi(r+1 takes ROOT)
+ *                      children CL[0][r], CR[r][m-1]; head of word r+1 = 0
+ *   1  CR[s][t], s < t r = s+1..t: IR[s][r] + CR[r][t]     children: those two
+ *   2  CL[s][t], s < t r = s..t-1: CL[s][r] + IL[r][t]     children: those two
+ *   3  IR[s][t]        r = s..t-1: CR[s][r] + CL[r+1][t]   children: those two;
+ *                      node lo+t takes lo+s
+ *   4  IL[s][t]        as kind 3; node lo+s takes lo+t
+ * The start item is kind 0, CR[0][m-1] without single_root; items of kinds 1
+ * and 2 with s = t are leaves; the order in which pending items are expanded
+ * does not matter.  The draw of an item:
+ *   masses  q_r = expf(term_r - M), M the largest term, 0 for a -inf term;
+ *   draw    u = (x >> 8) * 2^-24, x the first word of Philox4x32-10 at counter
+ *           (kind << 16 | s << 8 | t, sample, graph, 0x50000000) with the
+ *           64-bit seed as key (low word first).  With inclusive prefix sums
+ *           c_r in ascending r and S the last, the chosen term is the smallest
+ *           r with q_r > 0 and c_r > u * S, the largest r with q_r > 0 if
+ *           rounding leaves none.
+ * A chosen term is finite, so both children have a derivation: a returned
+ * sample is a projective tree over allowed arcs with the right ROOT count by
+ * construction; S not > 0 is the only dead end.
+ * Outputs: heads[g][s][i] the head of word i, -1 on row 0, rows >= n and where
+ * status != 1; log_prob[g][s] = sum_d ln probs_head[d][head_d] - ln Z (the
+ * terms logf in fp32, summed in double in word order), -inf where status != 1;
+ * status[g][s] = 1 drawn, 0 n < 2, 2 no projective tree, ln Z not finite or a
+ * dead end (the graphs of ggnn_projective_marginals' status 0 / 2); logz[g]
+ * (when not NULL) as ggnn_projective_marginals defines it: 0 for status 0,
+ * -inf for no projective tree.  Sample s of graph g depends on (seed, g, s)
+ * alone, not on num_samples.
+ * Storage: four fp32 triangular tables, 8 m (m + 1) bytes.  A graph with n <=
+ * GGNN_PROJ_SAMPLE_LDS_MAXN keeps them in LDS (132,096 B at 128, 141,320 B
+ * with c[], the four waves' item stacks and head rows), a larger one in
+ * `workspace`, per (graph, chunk of GGNN_PROJ_SAMPLE_CHUNK consecutive
+ * samples); the tier follows the graph's n.  At most m - 1 items are pending
+ * at once (their spans lie side by side), so a stack of GGNN_TREE_MAXV entries
+ * cannot overflow.  ggnn_projective_sample_workspace_bytes(b, v, K) is 0 for v
+ * <= GGNN_PROJ_SAMPLE_LDS_MAXN and b * ceil(K / GGNN_PROJ_SAMPLE_CHUNK) * 8 * v
+ * * (v + 1) above; a smaller workspace is rejected.  Needs v <= o, v <=
+ * GGNN_TREE_MAXV, o <= 1024, 1 <= num_samples <= GGNN_SAMPLE_MAX.  One
+ * workgroup per (graph, chunk): it fills the tables, then each of its four
+ * waves walks the chunk's samples wave, wave + 4, ...  No atomics, nothing
+ * between workgroups, every loop bounded by a function of n, every reduction
+ * and scan in a fixed order.  Stream-ordered, allocation-free, legal under
+ * stream capture, bit-reproducible; booked under the heads kernel kind. */
+#define GGNN_PROJ_SAMPLE_LDS_MAXN 128
+#define GGNN_PROJ_SAMPLE_CHUNK 16
+size_t ggnn_projective_sample_workspace_bytes(int32_t b, int32_t v, int32_t num_samples);
+int ggnn_projective_sample(const ggnn_dims* d,           /* b, v used */
+                           const float* probs_head,      /* device [b][v][o] */
+                           int32_t o,
+                           const int32_t* n_nodes,       /* device [b] */
+                           int32_t single_root,          /* 0 / 1 */
+                           int32_t num_samples, uint64_t seed,
+                           int32_t* heads,               /* device [b][K][v] out */
+                           float* log_prob,              /* device [b][K] out */
+                           int32_t* status,              /* device [b][K] out */
+                           float* logz,                  /* device [b] out, or NULL */
+                           void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */

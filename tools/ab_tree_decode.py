@@ -82,6 +82,23 @@ batch); writes its lines to profiles/tree_sample_ab.jsonl (--out) too; per line
   differ, samples  the K = 4 samples of the first 8 graphs that are not the
                    float64 host form's trees (all explained: asserted)
   log_prob_err     the largest |log_prob - float64| of those samples
+
+    python tools/ab_tree_decode.py --projective-sample
+
+alternates, in one process, ggnn_projective_marginals (the yardstick: the
+sampler runs its inside passes and leaves the outside pass out) and
+ggnn_projective_sample at K = 1, 4, 16 and 64 samples per graph, flat regime,
+median of 5 windows, and times the float64 host form
+(evaluation.projective_sample_arrays, K = 1, the first 8 graphs, scaled to the
+batch); writes its lines to profiles/proj_sample_ab.jsonl (--out) too; per line
+  chunk            GGNN_PROJ_SAMPLE_CHUNK of the library that ran
+  marg_ms          ggnn_projective_marginals (without scores)
+  sample_k1_ms / sample_k4_ms / sample_k16_ms / sample_k64_ms   the sampler alone
+  k1_not_slower    sample_k1_ms <= marg_ms
+  host_sample_ms   the fetch + the host form, K = 1
+  differ, samples  the K = 4 samples of the first 8 graphs that are not the
+                   float64 host form's trees (all explained: asserted)
+  log_prob_err     the largest |log_prob - float64| of those samples
 """
 import argparse
 import json
@@ -375,6 +392,52 @@ def tree_sample_sizes(torch, sizes, emit):
             emit(out)
 
 
+def projective_sample_sizes(torch, sizes, emit):
+    from ggnn_amd import _lib
+    from ggnn_amd import evaluation as E
+    from ggnn_amd.heads import OutputHeads
+    dev = torch.device("cuda", 0)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    oh = OutputHeads(64)
+    ks = (1, 4, 16, 64)
+    for (b, v, o) in sizes:
+        ph, _, n = batch(b, v, o, 46, "flat", seed=b + v)
+        ph_d, n_d = (torch.from_numpy(x).to(dev) for x in (ph, n))
+
+        def marginals():
+            return oh.projective_marginals(ph_d, n_d, True, with_scores=False)
+
+        def sampler(k):
+            return lambda: oh.projective_sample(ph_d, n_d, k, 1, True)
+
+        calls = 40 if b * v <= 2048 else 5
+        t = alternated(torch, [marginals] + [sampler(k) for k in ks], calls=calls)
+        out = {"b": b, "v": v, "o": o, "regime": "flat", "compute_units": cus, "chunk": _lib.PROJ_SAMPLE_CHUNK}
+        for key, x in zip(["marg_ms"] + ["sample_k%d_ms" % k for k in ks], t):
+            out[key], out[key + "_min"], out[key + "_max"] = x
+        out["k1_not_slower"] = out["sample_k1_ms"] <= out["marg_ms"]
+        heads, log_prob, status, _ = oh.projective_sample(ph_d, n_d, 4, 1, True)
+        torch.cuda.synchronize()
+        k = min(b, 8)                                                 # (the float64 host form: the first 8 graphs)
+        n_h = n[:k]
+        tm = time.perf_counter()
+        E.projective_sample_arrays(ph_d[:k].cpu().numpy(), n_h, 1, 1, True)
+        out["host_sample_ms"] = (time.perf_counter() - tm) * 1e3 * b / k
+        out["host_sample_graphs"] = k
+        h_heads, h_lp, h_status, margin, _ = E.projective_sample_arrays(ph[:k], n_h, 4, 1, True)
+        span_max = E.projective_marginals_arrays(ph[:k], n_h, True)[4]
+        assert np.array_equal(status[:k].cpu().numpy(), h_status)
+        got = heads[:k].cpu().numpy()
+        diff = (got != h_heads).any(axis=2) & (h_status == 1)
+        bar = lambda g: 4 * n_h[g] * (np.log2(n_h[g]) + 4 + span_max[g]) * 2.0 ** -24
+        assert all(margin[g, s] < bar(g) for g, s in np.argwhere(diff))
+        assert all(E.is_projective(got[g, s], n_h[g]) for g, s in np.argwhere(h_status == 1))
+        same = ~diff & (h_status == 1)
+        out["samples"], out["differ"] = int((h_status == 1).sum()), int(diff.sum())
+        out["log_prob_err"] = float(np.abs(log_prob[:k].cpu().numpy().astype(np.float64) - h_lp)[same].max())
+        emit(out)
+
+
 def epoch_tree_mbr(torch, emit):
     from ggnn_amd import evaluation as E
     from ggnn_amd.batching import DATA_DIR, TRAIN_WITH_DEV, read_btb_json, wsj_model_sizes
@@ -501,9 +564,12 @@ def main():
                          "and the \"mbr\" chain (and tree=True against tree=\"mbr\" with --epoch)")
     ap.add_argument("--tree-sample", action="store_true",
                     help="alternate ggnn_tree_marginals with ggnn_tree_sample at 1, 4 and 16 samples per graph")
+    ap.add_argument("--projective-sample", action="store_true",
+                    help="alternate ggnn_projective_marginals with ggnn_projective_sample at 1, 4, 16 and 64 samples "
+                         "per graph")
     ap.add_argument("--out", default=None,
-                    help="where --tree-marginals / --tree-sample also write their lines (default: profiles/"
-                         "tree_marginals_ab.jsonl / profiles/tree_sample_ab.jsonl)")
+                    help="where --tree-marginals / --tree-sample / --projective-sample also write their lines "
+                         "(default: profiles/tree_marginals_ab.jsonl / tree_sample_ab.jsonl / proj_sample_ab.jsonl)")
     ap.add_argument("--sizes", default="20x40x150,256x128x150")
     args = ap.parse_args()
     import torch
@@ -511,8 +577,9 @@ def main():
     head = {"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}
     print(json.dumps(head), flush=True)
     sizes = [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")]
-    if args.tree_marginals or args.tree_sample:
-        name = "tree_sample_ab.jsonl" if args.tree_sample else "tree_marginals_ab.jsonl"
+    if args.tree_marginals or args.tree_sample or args.projective_sample:
+        name = ("proj_sample_ab.jsonl" if args.projective_sample
+                else "tree_sample_ab.jsonl" if args.tree_sample else "tree_marginals_ab.jsonl")
         with open(args.out or os.path.join(ROOT, "profiles", name), "w") as f:
             def emit(line):
                 text = json.dumps(line)
@@ -520,6 +587,9 @@ def main():
                 f.write(text + "\n")
                 f.flush()
             f.write(json.dumps(head) + "\n")
+            if args.projective_sample:
+                projective_sample_sizes(torch, sizes, emit)
+                return
             if args.tree_sample:
                 tree_sample_sizes(torch, sizes, emit)
                 return
