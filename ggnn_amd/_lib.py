@@ -39,6 +39,7 @@ EXPORTED = (
     "ggnn_tree_loss_workspace_bytes", "ggnn_tree_loss", "ggnn_tree_loss_dev",
     "ggnn_tree_sample_workspace_bytes", "ggnn_tree_sample",
     "ggnn_projective_sample_workspace_bytes", "ggnn_projective_sample",
+    "ggnn_projective_kbest_lds_maxn", "ggnn_projective_kbest_workspace_bytes", "ggnn_projective_kbest",
 )
 DECODE_COUNTS = 5   # include/ggnn.h GGNN_DECODE_COUNTS: n_kept, las, uas, lab, regular
 TREE_MAXV = 256                # include/ggnn.h GGNN_TREE_MAXV
@@ -50,6 +51,7 @@ SAMPLE_LDS_MAXN = 199          # include/ggnn.h GGNN_SAMPLE_LDS_MAXN
 SAMPLE_MAX = 4096              # include/ggnn.h GGNN_SAMPLE_MAX
 PROJ_SAMPLE_LDS_MAXN = 128     # include/ggnn.h GGNN_PROJ_SAMPLE_LDS_MAXN
 PROJ_SAMPLE_CHUNK = 16         # include/ggnn.h GGNN_PROJ_SAMPLE_CHUNK
+KBEST_MAX = 16                 # include/ggnn.h GGNN_KBEST_MAX
 NUM_KERNEL_KINDS = 11
 
 
@@ -182,6 +184,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
         lib.ggnn_projective_sample.restype = _I
         lib.ggnn_projective_sample.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_uint64, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+        lib.ggnn_projective_kbest_lds_maxn.restype = ctypes.c_int32
+        lib.ggnn_projective_kbest_lds_maxn.argtypes = [ctypes.c_int32]
+        lib.ggnn_projective_kbest_workspace_bytes.restype = ctypes.c_size_t
+        lib.ggnn_projective_kbest_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        lib.ggnn_projective_kbest.restype = _I
+        lib.ggnn_projective_kbest.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
+                                              _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
         lib.ggnn_arc_confidence.restype = _I
         lib.ggnn_arc_confidence.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, _P, _P]
         lib.ggnn_dbg_gemm.restype = _I

@@ -32,6 +32,7 @@
 #include "k_pairs.h"
 #include "k_tree_sample.h"
 #include "k_proj_sample.h"
+#include "k_proj_kbest.h"
 
 // ---------------------------------------------------------------------------
 // error handling (thread-local last error; no exception crosses the ABI)
@@ -1967,6 +1968,40 @@ int ggnn_projective_sample(const ggnn_dims* d, const float* probs_head, int32_t 
                      (const int*)n_nodes, (int)d->v, (int)single_root, (int)num_samples, (int)chunks,
                      (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob, (int*)status, logz,
                      need ? (float*)workspace : nullptr, (long)4 * PROJ_TRI((long)d->v));
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+
+// the K best projective trees of the integer head scores (k_proj_kbest.h);
+// booked under the heads kind
+static_assert(GGNN_KBEST_MAX == KBEST_MAX, "projective k-best constants");
+int32_t ggnn_projective_kbest_lds_maxn(int32_t K) {
+  if (K < 1 || K > GGNN_KBEST_MAX) return 0;
+  int32_t n = 1;
+  while (n < GGNN_TREE_MAXV && PROJ_TRI((long)(n + 1)) * KBEST_SPAN_INTS(K) <= KBEST_TAB_INTS) ++n;
+  return n;
+}
+size_t ggnn_projective_kbest_workspace_bytes(int32_t b, int32_t v, int32_t K) {
+  if (b < 1 || v < 1 || K < 1 || K > GGNN_KBEST_MAX || v <= ggnn_projective_kbest_lds_maxn(K)) return 0;
+  return (size_t)b * sizeof(int32_t) * (size_t)PROJ_TRI((size_t)v) * KBEST_SPAN_INTS((size_t)K);
+}
+int ggnn_projective_kbest(const ggnn_dims* d, const int32_t* scores, int32_t o, const int32_t* n_nodes,
+                          int32_t single_root, int32_t K, int32_t* heads, int32_t* totals, int32_t* count,
+                          int32_t* status, void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  const char* const name = "projective_kbest";
+  const bool null_arg = !scores || !n_nodes || !heads || !totals || !count || !status;
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
+  if (K < 1 || K > GGNN_KBEST_MAX)
+    return fail(GGNN_EINVAL, "projective_kbest: K must lie in 1.." + std::to_string(GGNN_KBEST_MAX) + " (got " +
+                                 std::to_string(K) + ")");
+  const size_t need = ggnn_projective_kbest_workspace_bytes(d->b, d->v, K);
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Prof p(K_HEADS, s);
+  hipLaunchKernelGGL(k_projective_kbest<256>, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
+                     (const int*)n_nodes, (int)d->v, (int)single_root, (int)K, (int*)heads, (int*)totals, (int*)count,
+                     (int*)status, need ? (int*)workspace : nullptr,
+                     (long)PROJ_TRI((long)d->v) * KBEST_SPAN_INTS((long)K));
   LAUNCHCHK();
   return GGNN_OK;
 }

@@ -1,8 +1,9 @@
 """Decoding: the chain decode -> marginals -> tree / projective pass ->
-confidences -> samples, written once against a backend with the device
-binding's eight methods (``decode``, ``tree_decode``, ``projective_decode``,
-``projective_marginals``, ``tree_marginals``, ``arc_confidence``,
-``tree_sample``, ``projective_sample``):
+confidences -> samples -> k-best, written once against a backend with the
+device binding's nine methods (``decode``, ``tree_decode``,
+``projective_decode``, ``projective_marginals``, ``tree_marginals``,
+``arc_confidence``, ``tree_sample``, ``projective_sample``,
+``projective_kbest``):
 heads.OutputHeads on the GPU, ``HostDecoder`` over evaluation.*_arrays for a
 model on a CPU device; and the model's decoding entries (``DecodingMixin``)."""
 from __future__ import annotations
@@ -81,7 +82,7 @@ def _in_place(host_form):
 
 
 class HostDecoder:
-    """OutputHeads' eight decoding methods over the host forms, numpy in and
+    """OutputHeads' nine decoding methods over the host forms, numpy in and
     out; the marginals as float32, without the host forms' span_max / cond /
     margin."""
     tree_decode = _in_place(_eval.tree_decode_arrays)
@@ -116,6 +117,11 @@ class HostDecoder:
                                                                           single_root)
         return heads, log_prob.astype(np.float32), status, logz.astype(np.float32)
 
+    def projective_kbest(self, scores, n_nodes, K, single_root=True):
+        """(heads int32 [b, K, v], totals int32 [b, K], count int32 [b], status
+        int32 [b]) of evaluation.projective_kbest_arrays."""
+        return _eval.projective_kbest_arrays(scores, n_nodes, K, single_root)
+
 
 def _select(keep, x, fill):
     """x where keep, ``fill`` elsewhere: int32, in x's own array type."""
@@ -125,7 +131,7 @@ def _select(keep, x, fill):
 
 
 def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=True, confidence=False, samples=0,
-                 sample_seed=0, sample_family="nonprojective"):
+                 sample_seed=0, sample_family="nonprojective", kbest=0):
     """The decode and what follows it, in launch order and in ``backend``'s
     array type (probs [b, v, o], probs_e [b, v, oe] float32, n_nodes int32
     [b], labels: the two heads' targets or None).  mode True / "projective":
@@ -142,13 +148,19 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     sampled_heads [b, K, v], sample_log_prob [b, K], sample_status [b, K] (2
     where a graph is not regular); sample_family="projective" draws them from
     the distribution over projective trees instead (backend.projective_sample
-    on n * regular, which needs no marginals)."""
+    on n * regular, which needs no marginals).  kbest = K > 0: the K best
+    projective trees per graph in order (backend.projective_kbest on n *
+    regular) of tree_scores of the head PROBABILITIES -- the scores the chain
+    built for mode True / "projective", never an MBR mode's marginal scores --
+    as kbest_heads [b, K, v], kbest_total [b, K], kbest_count [b] and
+    kbest_status [b] (2 where a graph is not regular); kbest = 0 launches
+    nothing and adds nothing."""
     sample_family = _sample_family(sample_family)
     on_device, family, confidence = isinstance(probs, torch.Tensor), _MBR_FAMILY.get(mode), _confidence_mode(confidence)
     marginals = lambda kind: backend.projective_marginals if kind == "projective" else backend.tree_marginals
     pred, gold, counts = backend.decode([probs, probs_e], n_nodes, labels)
     regular = counts[:, 4] == 1
-    n_reg = _select(regular, n_nodes, 0) if mode or confidence or samples else None
+    n_reg = _select(regular, n_nodes, 0) if mode or confidence or samples or kbest else None
     if family:
         marg, logz, scores, has_marg = marginals(family)(probs, n_reg, single_root)
         pred, gold, counts = backend.decode([marg, probs_e], n_nodes, labels)
@@ -172,6 +184,12 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     if samples:
         out["sampled_heads"], out["sample_log_prob"] = heads, log_prob
         out["sample_status"] = _select(counts[:, 4:5] == 1, status, 2)
+    if kbest:
+        if family or not mode:       # (the chain's scores are the marginals', or there are none)
+            scores = (tree_scores if on_device else _eval.tree_scores)(probs, n_nodes, probs.shape[1])
+        out["kbest_heads"], out["kbest_total"], out["kbest_count"], status = backend.projective_kbest(
+            scores, n_reg, kbest, single_root)
+        out["kbest_status"] = _select(counts[:, 4] == 1, status, 2)
     return out
 
 
@@ -210,7 +228,7 @@ class DecodingMixin:
         return loss
 
     def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False, samples=0,
-                        sample_seed=0, sample_family="nonprojective"):
+                        sample_seed=0, sample_family="nonprojective", kbest=0):
         """_eval_forward of a feed (default: the staged one), then decode_chain
         eagerly on the same stream (never inside a captured step).  Returns a
         dict: loss (scalar tensor), ph (the staged placeholders), b, v, n_nodes
@@ -218,7 +236,8 @@ class DecodingMixin:
         gold / counts / tree_status / head_confidence / log_partition: device
         tensors, numpy arrays on a CPU device (HostDecoder), None without
         n_nodes or where tree / confidence (predict_batch's) do not ask; with
-        samples > 0 also sampled_heads / sample_log_prob / sample_status."""
+        samples > 0 also sampled_heads / sample_log_prob / sample_status, with
+        kbest > 0 also kbest_heads / kbest_total / kbest_count / kbest_status."""
         mode = _tree_mode(tree, confidence, "_decode_forward")
         loss = self._eval_forward(self.placeholders if feed_dict is None else feed_dict)
         ph = dict(self.placeholders)
@@ -238,7 +257,7 @@ class DecodingMixin:
             labels = [np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o),
                       np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)] if with_gold else None
         r.update(decode_chain(backend, probs, probs_e, n, labels if with_gold else None, mode, single_root, confidence,
-                              samples, sample_seed, sample_family))
+                              samples, sample_seed, sample_family, kbest))
         return r
 
     def _host_pred(self, ph, b, v):
@@ -251,7 +270,7 @@ class DecodingMixin:
                                      np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
 
     def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False, samples=0, sample_seed=0,
-                      sample_family="nonprojective"):
+                      sample_family="nonprojective", kbest=0):
         """The predicted tree of every graph of a batch: {'heads': [b, v],
         'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
         arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
@@ -303,13 +322,32 @@ class DecodingMixin:
         distribution of tree="projective-mbr", confidence="projective" and
         structured_loss="projective"; every returned tree is projective and
         'sample_log_prob' is normalised by that distribution's Z); the keys and
-        their shapes are the same.  Any other value is a ValueError."""
+        their shapes are the same.  Any other value is a ValueError.
+        kbest = K in 1..KBEST_MAX: the dict gains 'kbest_heads' [b, K, v]
+        int32, the K best PROJECTIVE trees of every graph, best first
+        (ggnn_projective_kbest on tree_scores of the head probabilities,
+        whatever ``tree`` is; rank 0 has tree="projective"'s total), -1 on node
+        0, padding and the ranks >= 'kbest_count' [b] (the trees returned:
+        min(K, number of projective trees)); 'kbest_status' [b] int32: 1 = count
+        >= 1, 0 = fewer than two nodes, 2 = no projective tree exists, scores
+        out of range or not attempted (an irregular graph, a feed whose masks
+        are not in closed form: count 0); 'kbest_log_prob' [b, K] float32 =
+        total * ln 2 / 2^k, k = tree_score_shift(v), computed on the host in
+        float64 from the integer totals: the ln of the product of the tree's
+        head probabilities AT THE RESOLUTION OF THE SCORES (every log2 p
+        rounded to 2^-k bits and clamped below at -150; not normalised by any
+        Z), -inf on the ranks >= count.  kbest = 0 launches nothing and adds
+        nothing; anything outside 0..KBEST_MAX is a ValueError."""
         tree = _tree_mode(tree, confidence, "predict_batch")
         sample_family = _sample_family(sample_family)
         samples = int(samples)
         if not 0 <= samples <= _eval.SAMPLE_MAX:
             raise ValueError("samples must lie in 0..%d (got %d)" % (_eval.SAMPLE_MAX, samples))
-        r = self._decode_forward(feed_dict, False, tree, single_root, confidence, samples, sample_seed, sample_family)
+        kbest = int(kbest)
+        if not 0 <= kbest <= _eval.KBEST_MAX:
+            raise ValueError("kbest must lie in 0..%d (got %d)" % (_eval.KBEST_MAX, kbest))
+        r = self._decode_forward(feed_dict, False, tree, single_root, confidence, samples, sample_seed, sample_family,
+                                 kbest)
         ph, b, v, pred = r["ph"], r["b"], r["v"], r["pred"]
         if pred is None:
             pred = self._host_pred(ph, b, v)
@@ -334,7 +372,39 @@ class DecodingMixin:
                 r["sample_status"] = np.full((b, samples), 2, np.int32)
             for k in ("sampled_heads", "sample_log_prob", "sample_status"):
                 out[k] = _as_np(r[k])
+        if kbest:
+            if r.get("kbest_heads") is None:        # masks not in closed form: not attempted
+                r["kbest_heads"] = np.full((b, kbest, v), -1, np.int32)
+                r["kbest_total"] = np.full((b, kbest), _eval.TREE_FORBIDDEN, np.int32)
+                r["kbest_count"], r["kbest_status"] = np.zeros(b, np.int32), np.full(b, 2, np.int32)
+            for k in ("kbest_heads", "kbest_count", "kbest_status"):
+                out[k] = _as_np(r[k])
+            total = _as_np(r["kbest_total"]).astype(np.float64)
+            present = np.arange(kbest)[None, :] < out["kbest_count"][:, None]
+            scale = np.log(2.0) / 2.0 ** _eval.tree_score_shift(v)
+            out["kbest_log_prob"] = np.where(present, total * scale, -np.inf).astype(np.float32)
         return out
+
+    def parse_kbest(self, raw_data, k, single_root=True):
+        """The k best projective dependency trees of raw btb sentences
+        (parse's input), best first (predict_batch(kbest=k)).  Returns (trees,
+        log_probs): trees[s] a list of up to k entries in the JSON's 'targets'
+        form [[head, label], ...] for nodes 1..n-1 (the label one-based: the
+        label head's arg-max, which does not depend on the head), log_probs[s]
+        each one's 'kbest_log_prob', aligned and non-increasing.  A sentence
+        with fewer than k projective trees yields those it has; a sentence
+        process_raw_graphs drops yields []."""
+        raw = [{"targets": [], **d, "id": i} for i, d in enumerate(raw_data)]
+        out, log_probs = [[] for _ in raw], [[] for _ in raw]
+        data = self.process_raw_graphs(raw, False)
+        for feed in self.make_minibatch_iterator(data, False):
+            p = self.predict_batch(feed, False, single_root, kbest=k)
+            for g, s in enumerate(p["sentences_id"]):
+                n = int(p["n_nodes"][g])
+                for r in range(int(p["kbest_count"][g])):
+                    out[s].append([[int(h), int(l) + 1] for h, l in zip(p["kbest_heads"][g, r, 1:n], p["labels"][g, 1:n])])
+                    log_probs[s].append(float(p["kbest_log_prob"][g, r]))
+        return out, log_probs
 
     def sample_trees(self, raw_data, num_samples, single_root=True, seed=0, family="nonprojective"):
         """Dependency trees of raw btb sentences (parse's input) drawn from the

@@ -672,6 +672,156 @@ def random_projective_heads(n, rng):
     return heads
 
 
+# ------------------------------------------------- k-best projective trees
+# Host form of ``ggnn_projective_kbest`` (include/ggnn.h, csrc/k_proj_kbest.h):
+# _eisner's tables with a sorted list of up to K entries per item.  IR and IL of
+# a span share the base list BS (they differ by the arc's score alone).  A
+# candidate of an item is (split, rank in the first child, rank in the second
+# child); a list is the first K candidates in the total order: larger total
+# first, then the smaller split, the smaller first rank, the smaller second
+# rank.  Candidate (r, i, j) has (i + 1)(j + 1) - 1 candidates of its split
+# ahead of it, so only the pairs with (i + 1)(j + 1) <= K are formed.  Every
+# entry keeps its (split, i, j) packed as split << 8 | i << 4 | j; the trees are
+# read back from those.
+KBEST_MAX = 16                 # GGNN_KBEST_MAX
+
+
+def _kbest_take(tot, K):
+    """tot int64 [C, spans]: the candidates' totals in the order (split, i, j)
+    along axis 0 (_PROJ_NEG = no such candidate), C >= K.  Returns (values [K,
+    spans], candidate indices [K, spans]) of the first K in the total order (a
+    stable sort by descending total keeps the order of equals)."""
+    order = np.argsort(-tot, axis=0, kind="stable")[:K]
+    return np.take_along_axis(tot, order, axis=0), order
+
+
+def _kbest_tables(s, n, single_root, K):
+    """The lists of one graph: (CR, CL, BS values [K, m, m] by (rank, d, s),
+    their back-pointers, the final list's values [K] and back-pointers [K])."""
+    lo = 1 if single_root else 0
+    m = n - lo
+    full = np.asarray(s)[:n, :n].astype(np.int64)
+    w = full[lo:, lo:].copy()                  # w[i, j]: position i takes head at position j
+    w[full[lo:, lo:] == TREE_FORBIDDEN] = _PROJ_NEG
+    w[np.arange(m), np.arange(m)] = _PROJ_NEG
+    if not single_root:
+        w[0, :] = _PROJ_NEG                    # node 0 is never a dependent
+    pairs = np.asarray([(i, j) for i in range(K) for j in range(K // (i + 1))], np.int64)
+    pi, pj = pairs[:, 0][None, :, None], pairs[:, 1][None, :, None]
+    code = (pairs[:, 0] << 4) | pairs[:, 1]
+    CR = np.full((K, m, m), _PROJ_NEG, np.int64)
+    CL, BS = CR.copy(), CR.copy()
+    CRB, CLB, BSB = (np.zeros((K, m, m), np.int64) for _ in range(3))
+    CR[0, 0, :] = CL[0, 0, :] = 0
+
+    def take(tot, L):
+        val, idx = _kbest_take(tot.reshape(-1, m - L), K)
+        return val, np.where(val == _PROJ_NEG, 0, ((idx // len(code)) << 8) | code[idx % len(code)])
+
+    for L in range(1, m):
+        st = np.arange(m - L)[None, None, :]
+        k = np.arange(L)[:, None, None]
+        sl = np.arange(m - L)
+        BS[:, L, sl], BSB[:, L, sl] = take(_proj_add(CR[pi, k, st], CL[pj, L - 1 - k, st + k + 1]), L)
+        ar = w[st + k + 1, st]                 # word s+k+1 takes head s
+        al = w[st + k, st + L]                 # word s+k takes head t
+        CR[:, L, sl], CRB[:, L, sl] = take(_proj_add(_proj_add(BS[pi, k + 1, st], ar), CR[pj, L - 1 - k, st + k + 1]), L)
+        CL[:, L, sl], CLB[:, L, sl] = take(_proj_add(_proj_add(CL[pi, k, st], al), BS[pj, L - k, st + k]), L)
+    if single_root:
+        p = np.arange(m)[:, None, None]
+        root = full[1:, 0].copy()
+        root[root == TREE_FORBIDDEN] = _PROJ_NEG
+        tot = _proj_add(_proj_add(CL[pi, p, 0], root[p]), CR[pj, m - 1 - p, p])
+        val, idx = _kbest_take(tot.reshape(-1, 1), K)
+        fv, fb = val[:, 0], (((idx // len(code)) << 8) | code[idx % len(code)])[:, 0]
+    else:
+        fv, fb = CR[:, m - 1, 0].copy(), np.zeros(K, np.int64)
+    return (CR, CL, BS), (CRB, CLB, BSB), fv, fb
+
+
+def _kbest_walk(backs, fb, rank, n, single_root):
+    """The heads (list, [0] is -1) of the final list's entry ``rank``."""
+    lo = 1 if single_root else 0
+    m = n - lo
+    heads = [-1] * n
+    stack = []
+
+    def push(kind, r, a, b):                   # kinds: 0 CR, 1 CL, 2 BS under a -> b, 3 BS under b -> a
+        if a < b:
+            stack.append((kind, r, a, b))
+
+    if single_root:
+        bp = int(fb[rank])
+        p = bp >> 8
+        heads[lo + p] = 0
+        push(1, (bp >> 4) & 15, 0, p)
+        push(0, bp & 15, p, m - 1)
+    else:
+        push(0, rank, 0, m - 1)
+    while stack:
+        kind, r, a, b = stack.pop()
+        bp = int(backs[min(kind, 2)][r, b - a, a])
+        k, i, j = bp >> 8, (bp >> 4) & 15, bp & 15
+        if kind == 0:
+            push(2, i, a, a + k + 1)
+            push(0, j, a + k + 1, b)
+        elif kind == 1:
+            push(1, i, a, a + k)
+            push(3, j, a + k, b)
+        else:
+            if kind == 2:
+                heads[lo + b] = lo + a
+            else:
+                heads[lo + a] = lo + b
+            push(0, i, a, a + k)
+            push(1, j, a + k + 1, b)
+    return heads
+
+
+def projective_kbest_arrays(scores, n_nodes, K, single_root=True):
+    """The host form of ``ggnn_projective_kbest`` (include/ggnn.h): the K best
+    projective trees of every graph in order.  scores int32 [b, v, o]
+    (``tree_scores``), n_nodes [b], 1 <= K <= KBEST_MAX.  Returns (heads int32
+    [b, K, v]: the head of word i in the tree of rank k, -1 on node 0, rows >=
+    n and ranks >= count; totals int32 [b, K]: the tree's sum of scores,
+    TREE_FORBIDDEN on ranks >= count; count int32 [b]; status int32 [b]: 0 = n
+    < 2, 1 = count >= 1, 2 = S * (n - 1) >= 2^30 for the largest absolute
+    allowed score S, or no projective tree exists).  Rank 0 is _eisner's tree,
+    ties included; the list for K is a prefix of the list for a larger K."""
+    s = np.asarray(scores)
+    if s.ndim != 3 or s.dtype != np.int32:
+        raise ValueError("scores must be int32 [b, v, o]")
+    b, v, o = s.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("projective k-best needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    K = int(K)
+    if not 1 <= K <= KBEST_MAX:
+        raise ValueError("K must lie in 1..%d (got %d)" % (KBEST_MAX, K))
+    nn = _node_counts(n_nodes, b, v, o)
+    heads = np.full((b, K, v), -1, np.int32)
+    totals = np.full((b, K), TREE_FORBIDDEN, np.int32)
+    count, status = np.zeros(b, np.int32), np.zeros(b, np.int32)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2:
+            continue
+        status[g] = 2
+        a = s[g, 1:n, :n].astype(np.int64)
+        live = a != TREE_FORBIDDEN
+        live[np.arange(n - 1), np.arange(1, n)] = False
+        if int(np.abs(a[live]).max(initial=0)) * (n - 1) >= 2 ** 30:      # the range rule
+            continue
+        _, backs, fv, fb = _kbest_tables(s[g], n, bool(single_root), K)
+        c = int((fv != _PROJ_NEG).sum())
+        if c == 0:
+            continue
+        status[g], count[g] = 1, c
+        totals[g, :c] = fv[:c]
+        for r in range(c):
+            heads[g, r, :n] = _kbest_walk(backs, fb, r, n, bool(single_root))
+    return heads, totals, count, status
+
+
 # ------------------------------------------------- projective arc marginals
 # Host form of ``ggnn_projective_marginals`` (include/ggnn.h, csrc/k_marg.h):
 # the sum-product twin of _eisner (inside pass, explicit outside pass), in log

@@ -180,6 +180,7 @@ class OutputHeads:
         self._lapl_ws = None   # ggnn_tree_marginals' workspace (graphs above LAPL_LDS_MAXN nodes)
         self._sample_ws = None  # ggnn_tree_sample's workspace (graphs above SAMPLE_LDS_MAXN nodes)
         self._proj_sample_ws = None  # ggnn_projective_sample's workspace (graphs above PROJ_SAMPLE_LDS_MAXN nodes)
+        self._kbest_ws = None  # ggnn_projective_kbest's workspace (graphs above ggnn_projective_kbest_lds_maxn(K) nodes)
         self._loss_ws = None   # ggnn_tree_loss' workspace (n_eff, then the family's marginals workspace)
         self._saved = None
         # the last forward's structured loss (tree_loss=): the marginals that
@@ -539,6 +540,43 @@ class OutputHeads:
                                                     0 if workspace is None else workspace.numel(), _stream()),
                    "ggnn_projective_sample")
         return heads, log_prob, status, logz
+
+    def projective_kbest(self, scores, n_nodes, K, single_root=True, workspace=None):
+        """The K best projective dependency trees of every graph, best first,
+        on the current stream (ggnn_projective_kbest: Eisner's tables with a
+        sorted list of up to K entries per item; rank 0 is
+        ``projective_decode``'s tree).  scores: int32 [b, v, o]
+        (``tree_scores``); n_nodes: int32 [b]; 1 <= K <= KBEST_MAX.  Returns
+        (heads int32 [b, K, v]: the head of word i in the tree of rank k, -1 on
+        node 0, the rows >= n and the ranks >= count; totals int32 [b, K]: the
+        tree's sum of scores, TREE_FORBIDDEN on the ranks >= count; count int32
+        [b]: the trees returned, min(K, number of projective trees); status
+        int32 [b]: 1 = count >= 1, 0 = n < 2, 2 = no projective tree exists or
+        the scores are out of range).  workspace: a uint8 tensor to use instead
+        of the binding's own (grown on demand; needed for v >
+        ggnn_projective_kbest_lds_maxn(K) only)."""
+        _check_tensor(scores, "scores", torch.int32)
+        b, v, o = scores.shape
+        dev = scores.device
+        if v > o or v > _lib.TREE_MAXV:
+            raise ValueError("projective_kbest needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
+        K = int(K)
+        if not 1 <= K <= _lib.KBEST_MAX:
+            raise ValueError("K must lie in 1..%d (got %d)" % (_lib.KBEST_MAX, K))
+        _check_n_nodes(n_nodes, b, dev)
+        need = int(self._lib.ggnn_projective_kbest_workspace_bytes(b, v, K))
+        workspace = self._workspace("_kbest_ws", need, dev, workspace)
+        heads = torch.empty(b, K, v, dtype=torch.int32, device=dev)
+        totals = torch.empty(b, K, dtype=torch.int32, device=dev)
+        count = torch.empty(b, dtype=torch.int32, device=dev)
+        status = torch.empty(b, dtype=torch.int32, device=dev)
+        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+        _lib.check(self._lib.ggnn_projective_kbest(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes),
+                                                   int(bool(single_root)), K, _ptr(heads), _ptr(totals), _ptr(count),
+                                                   _ptr(status), _ptr(workspace),
+                                                   0 if workspace is None else workspace.numel(), _stream()),
+                   "ggnn_projective_kbest")
+        return heads, totals, count, status
 
     def arc_confidence(self, marg, n_nodes, pred):
         """conf float32 [b, v]: marg[g, i, pred[g, i, 0]], 0 where there is no

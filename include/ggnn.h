@@ -801,6 +801,66 @@ int ggnn_projective_sample(const ggnn_dims* d,           /* b, v used */
                            float* logz,                  /* device [b] out, or NULL */
                            void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* The K best projective dependency trees of the integer head scores, in order
+ * (Huang & Chiang 2005 on Eisner's tables): what ggnn_projective_decode returns
+ * once, this returns K times.  scores, allowed arcs, the clamping of n, the
+ * positions p = 0..m-1 (lo / m), the four span kinds, the -2^30 sentinel and
+ * the range rule are ggnn_projective_decode's; a graph with S * (n - 1) >= 2^30
+ * gets status 2.  There is no pred and no fast path: the tables are always
+ * filled.  Every item holds a LIST of up to K entries.  IR and IL of a span
+ * differ by the arc's score alone and share one base list BS:
+ *   BS[s][t]  candidates (r, i, j), s <= r < t:  CR[s][r][i] + CL[r+1][t][j]
+ *   CR[s][t]  candidates (r, i, j), s < r <= t:  BS[s][r][i] + score(r takes s) + CR[r][t][j]
+ *   CL[s][t]  candidates (r, i, j), s <= r < t:  CL[s][r][i] + BS[r][t][j] + score(r takes t)
+ *   final     single_root: (p, i, j): CL[0][p][i] + CR[p][m-1][j] + score(p+1
+ *             takes ROOT); otherwise CR[0][m-1]'s list
+ * (i, j: ranks in the first / second entry's list).  A candidate exists when
+ * both entries exist and the arc is allowed; a list is the first K candidates
+ * in the total order: larger total first, then the smaller split r (p), then
+ * the smaller i, then the smaller j.  The result is a function of the inputs
+ * alone.  Every projective tree has exactly one derivation, so the final list
+ * holds min(K, number of projective trees) distinct trees; rank 0 is
+ * ggnn_projective_decode's tree, ties included; the list for K is a prefix of
+ * the list for any larger K.  Every entry stores its (split, i, j); the tree of
+ * a rank is read back from those, never found again by value.
+ * Outputs: heads[g][k][i] the head of word i in the tree of rank k, -1 on node
+ * 0, rows >= n and ranks >= count[g]; totals[g][k] = sum_i scores[i][head_i],
+ * GGNN_TREE_FORBIDDEN on ranks >= count[g]; count[g] in 0..K; status[g] = 0 n <
+ * 2 (count 0), 1 count >= 1, 2 the range rule is violated or no projective
+ * tree exists (count 0).
+ * Storage: per span 6 K + 2 int32 (three value lists, three back-pointer
+ * lists, two arc scores), m (m + 1) / 2 spans.  A graph with n <=
+ * ggnn_projective_kbest_lds_maxn(K) -- the largest n with n (n + 1) / 2 * (6 K
+ * + 2) <= 38400 ints: 97 at K = 1, 73 at 2, 27 at 16 -- keeps them in LDS
+ * (153,600 B; 161,940 B with the four waves' item stacks and head rows and the
+ * final list), a larger one in `workspace`, per graph; the tier follows the
+ * graph's n.  ggnn_projective_kbest_workspace_bytes(b, v, K) is 0 for v <=
+ * ggnn_projective_kbest_lds_maxn(K) and b * 2 * v * (v + 1) * (6 K + 2) above;
+ * a smaller workspace is rejected before any launch.  Fewer than m items are
+ * pending in a walk-back at once, so a stack of GGNN_TREE_MAXV entries cannot
+ * overflow; an overflow or a walk of more than 2 m - 1 items would be status
+ * 2.  Needs v <= o, v <= GGNN_TREE_MAXV, o <= 1024, 1 <= K <= GGNN_KBEST_MAX.
+ * One workgroup per graph: it fills the lists length by length (K rounds of
+ * "next in order" per item, a span's splits spread over a lane group), then
+ * each of its four waves reads back the ranks wave, wave + 4, ...  No atomics,
+ * nothing between workgroups, every loop bounded by a function of n and K.
+ * Stream-ordered, allocation-free, legal under stream capture,
+ * bit-reproducible; booked under the heads kernel kind. */
+#define GGNN_KBEST_MAX 16
+int32_t ggnn_projective_kbest_lds_maxn(int32_t K);
+size_t ggnn_projective_kbest_workspace_bytes(int32_t b, int32_t v, int32_t K);
+int ggnn_projective_kbest(const ggnn_dims* d,           /* b, v used */
+                          const int32_t* scores,        /* device [b][v][o] */
+                          int32_t o,
+                          const int32_t* n_nodes,       /* device [b] */
+                          int32_t single_root,          /* 0 / 1 */
+                          int32_t K,
+                          int32_t* heads,               /* device [b][K][v] out */
+                          int32_t* totals,              /* device [b][K] out */
+                          int32_t* count,               /* device [b] out */
+                          int32_t* status,              /* device [b] out */
+                          void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */

@@ -99,6 +99,21 @@ batch); writes its lines to profiles/proj_sample_ab.jsonl (--out) too; per line
   differ, samples  the K = 4 samples of the first 8 graphs that are not the
                    float64 host form's trees (all explained: asserted)
   log_prob_err     the largest |log_prob - float64| of those samples
+
+    python tools/ab_tree_decode.py --projective-kbest
+
+alternates, in one process, ggnn_projective_decode on a pred without heads (the
+yardstick: its pass runs on every graph and fills the 1-best tables) and
+ggnn_projective_kbest at K = 1, 4 and 16, flat regime, median of 5 windows, and
+times the host form (evaluation.projective_kbest_arrays, K = 4, the first 8
+graphs, scaled to the batch); writes its lines to profiles/proj_kbest_ab.jsonl
+(--out) too; per line
+  lds_maxn         ggnn_projective_kbest_lds_maxn(K) of the library that ran
+  decode_ms        the reset of pred + ggnn_projective_decode
+  kbest_k1_ms / kbest_k4_ms / kbest_k16_ms   ggnn_projective_kbest alone
+  host_kbest_k4_ms the host form, K = 4 (its outputs equal the kernel's bit for
+                   bit, and rank 0 is the decode's tree: asserted)
+  trees            the trees the K = 4 launch returned
 """
 import argparse
 import json
@@ -438,6 +453,45 @@ def projective_sample_sizes(torch, sizes, emit):
         emit(out)
 
 
+def projective_kbest_sizes(torch, sizes, emit):
+    from ggnn_amd import _lib
+    from ggnn_amd import evaluation as E
+    from ggnn_amd.heads import OutputHeads, tree_scores
+    dev = torch.device("cuda", 0)
+    oh = OutputHeads(64)
+    ks = (1, 4, 16)
+    for (b, v, o) in sizes:
+        ph, _, n = batch(b, v, o, 46, "flat", seed=b + v)
+        ph_d, n_d = (torch.from_numpy(x).to(dev) for x in (ph, n))
+        scores = tree_scores(ph_d, n_d, v)
+        pred = torch.empty(b, v, 2, dtype=torch.int32, device=dev)
+
+        def decode():
+            pred.fill_(-1)                                            # no tree: the pass runs on every graph
+            return oh.projective_decode(scores, n_d, pred)
+
+        def kbest(k):
+            return lambda: oh.projective_kbest(scores, n_d, k, True)
+
+        calls = 40 if b * v <= 2048 else 5
+        t = alternated(torch, [decode] + [kbest(k) for k in ks], calls=calls)
+        out = {"b": b, "v": v, "o": o, "regime": "flat",
+               "lds_maxn": {str(k): int(_lib.load().ggnn_projective_kbest_lds_maxn(k)) for k in ks}}
+        for key, x in zip(["decode_ms"] + ["kbest_k%d_ms" % k for k in ks], t):
+            out[key], out[key + "_min"], out[key + "_max"] = x
+        assert (decode().cpu().numpy() == 1).all()
+        got = [x.cpu().numpy() for x in kbest(4)()]
+        assert np.array_equal(got[0][:, 0], pred.cpu().numpy()[:, :, 0])    # rank 0: the decode's tree
+        k = min(b, 8)                                                 # (the host form: the first 8 graphs)
+        tm = time.perf_counter()
+        ref = E.projective_kbest_arrays(scores[:k].cpu().numpy(), n[:k], 4, True)
+        out["host_kbest_k4_ms"] = (time.perf_counter() - tm) * 1e3 * b / k
+        out["host_kbest_graphs"] = k
+        assert all(np.array_equal(a[:k], c) for a, c in zip(got, ref))       # bit-identical
+        out["trees"] = int(got[2].sum())
+        emit(out)
+
+
 def epoch_tree_mbr(torch, emit):
     from ggnn_amd import evaluation as E
     from ggnn_amd.batching import DATA_DIR, TRAIN_WITH_DEV, read_btb_json, wsj_model_sizes
@@ -567,9 +621,13 @@ def main():
     ap.add_argument("--projective-sample", action="store_true",
                     help="alternate ggnn_projective_marginals with ggnn_projective_sample at 1, 4, 16 and 64 samples "
                          "per graph")
+    ap.add_argument("--projective-kbest", action="store_true",
+                    help="alternate ggnn_projective_decode (its pass made to run) with ggnn_projective_kbest at K = 1, "
+                         "4 and 16")
     ap.add_argument("--out", default=None,
-                    help="where --tree-marginals / --tree-sample / --projective-sample also write their lines "
-                         "(default: profiles/tree_marginals_ab.jsonl / tree_sample_ab.jsonl / proj_sample_ab.jsonl)")
+                    help="where --tree-marginals / --tree-sample / --projective-sample / --projective-kbest also write "
+                         "their lines (default: profiles/tree_marginals_ab.jsonl / tree_sample_ab.jsonl / "
+                         "proj_sample_ab.jsonl / proj_kbest_ab.jsonl)")
     ap.add_argument("--sizes", default="20x40x150,256x128x150")
     args = ap.parse_args()
     import torch
@@ -577,8 +635,8 @@ def main():
     head = {"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}
     print(json.dumps(head), flush=True)
     sizes = [tuple(int(x) for x in s.split("x")) for s in args.sizes.split(",")]
-    if args.tree_marginals or args.tree_sample or args.projective_sample:
-        name = ("proj_sample_ab.jsonl" if args.projective_sample
+    if args.tree_marginals or args.tree_sample or args.projective_sample or args.projective_kbest:
+        name = ("proj_kbest_ab.jsonl" if args.projective_kbest else "proj_sample_ab.jsonl" if args.projective_sample
                 else "tree_sample_ab.jsonl" if args.tree_sample else "tree_marginals_ab.jsonl")
         with open(args.out or os.path.join(ROOT, "profiles", name), "w") as f:
             def emit(line):
@@ -587,6 +645,9 @@ def main():
                 f.write(text + "\n")
                 f.flush()
             f.write(json.dumps(head) + "\n")
+            if args.projective_kbest:
+                projective_kbest_sizes(torch, sizes, emit)
+                return
             if args.projective_sample:
                 projective_sample_sizes(torch, sizes, emit)
                 return
