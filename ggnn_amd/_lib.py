@@ -146,51 +146,25 @@ def load(path: str | None = None) -> ctypes.CDLL:
         lib.ggnn_heads_backward_dev.argtypes = [_DP, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]
         lib.ggnn_heads_decode.restype = _I
         lib.ggnn_heads_decode.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P]
-        lib.ggnn_tree_decode_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_tree_decode_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
-        lib.ggnn_tree_decode.restype = _I
-        lib.ggnn_tree_decode.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
-                                         ctypes.c_size_t, _P]
-        lib.ggnn_projective_decode_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_projective_decode_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
-        lib.ggnn_projective_decode.restype = _I
-        lib.ggnn_projective_decode.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
-                                               ctypes.c_size_t, _P]
-        lib.ggnn_projective_marginals_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_projective_marginals_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
-        lib.ggnn_projective_marginals.restype = _I
-        lib.ggnn_projective_marginals.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
-                                                  ctypes.c_size_t, _P]
-        lib.ggnn_tree_marginals_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_tree_marginals_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
-        lib.ggnn_tree_marginals.restype = _I
-        lib.ggnn_tree_marginals.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
-                                            ctypes.c_size_t, _P]
+        # the passes with a workspace: ggnn_<name>_workspace_bytes(b, v, + `sized` more int32) and
+        # ggnn_<name>(dims, input, o, n_nodes, single_root, <middle>, workspace, workspace_bytes, stream)
+        I32 = ctypes.c_int32
+        for name, sized, middle in (("tree_decode", 0, [_P] * 4), ("projective_decode", 0, [_P] * 4),
+                                    ("projective_marginals", 0, [_P] * 4), ("tree_marginals", 0, [_P] * 4),
+                                    ("tree_sample", 1, [_P, _P, _P, I32, U64, _P, _P, _P]),
+                                    ("projective_sample", 1, [I32, U64, _P, _P, _P, _P]),
+                                    ("projective_kbest", 1, [I32, _P, _P, _P, _P])):
+            size, entry = getattr(lib, "ggnn_%s_workspace_bytes" % name), getattr(lib, "ggnn_" + name)
+            size.restype, size.argtypes = ctypes.c_size_t, [I32] * (2 + sized)
+            entry.restype, entry.argtypes = _I, [_DP, _P, I32, _P, I32] + middle + [_P, ctypes.c_size_t, _P]
         lib.ggnn_tree_loss_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_tree_loss_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        lib.ggnn_tree_loss_workspace_bytes.argtypes = [I32, I32, I32]
         lib.ggnn_tree_loss.restype = _I
-        lib.ggnn_tree_loss.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32, F,
-                                       _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+        lib.ggnn_tree_loss.argtypes = [_DP, _P, I32, _P, _P, I32, I32, F] + [_P] * 6 + [ctypes.c_size_t, _P]
         lib.ggnn_tree_loss_dev.restype = _I
-        lib.ggnn_tree_loss_dev.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32, _P,
-                                           _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
-        lib.ggnn_tree_sample_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_tree_sample_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-        lib.ggnn_tree_sample.restype = _I
-        lib.ggnn_tree_sample.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, ctypes.c_int32,
-                                         ctypes.c_uint64, _P, _P, _P, _P, ctypes.c_size_t, _P]
-        lib.ggnn_projective_sample_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_projective_sample_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-        lib.ggnn_projective_sample.restype = _I
-        lib.ggnn_projective_sample.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_uint64, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
-        lib.ggnn_projective_kbest_lds_maxn.restype = ctypes.c_int32
-        lib.ggnn_projective_kbest_lds_maxn.argtypes = [ctypes.c_int32]
-        lib.ggnn_projective_kbest_workspace_bytes.restype = ctypes.c_size_t
-        lib.ggnn_projective_kbest_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-        lib.ggnn_projective_kbest.restype = _I
-        lib.ggnn_projective_kbest.argtypes = [_DP, _P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32,
-                                              _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+        lib.ggnn_tree_loss_dev.argtypes = [_DP, _P, I32, _P, _P, I32, I32, _P] + [_P] * 6 + [ctypes.c_size_t, _P]
+        lib.ggnn_projective_kbest_lds_maxn.restype = I32
+        lib.ggnn_projective_kbest_lds_maxn.argtypes = [I32]
         lib.ggnn_arc_confidence.restype = _I
         lib.ggnn_arc_confidence.argtypes = [_DP, _P, ctypes.c_int32, _P, _P, _P, _P]
         lib.ggnn_dbg_gemm.restype = _I

@@ -1702,6 +1702,39 @@ static int decode_workspace(const std::string& name, size_t need, const void* wo
                                  std::to_string(need) + " needed");
   return GGNN_OK;
 }
+// the checks more than one entry point makes of its own arguments
+static int given_together(const std::string& name, const char* a, const void* pa, const char* b, const void* pb) {
+  if ((pa == nullptr) == (pb == nullptr)) return GGNN_OK;
+  return fail(GGNN_EINVAL, name + ": " + a + " and " + b + " must be given together (one is NULL)");
+}
+static int no_alias(const std::string& name, const float* marg, const float* probs_head) {
+  return marg == probs_head ? fail(GGNN_EINVAL, name + ": marg must not alias probs_head") : GGNN_OK;
+}
+static int count_in_range(const std::string& name, const char* what, int32_t x, int32_t max) {
+  if (x >= 1 && x <= max) return GGNN_OK;
+  return fail(GGNN_EINVAL, name + ": " + what + " must lie in 1.." + std::to_string(max) + " (got " + std::to_string(x) + ")");
+}
+static int fits_grid(const std::string& name, const char* what, long blocks) {
+  return blocks > 0x7FFFFFFFL ? fail(GGNN_EINVAL, name + ": " + what + " exceeds the grid") : GGNN_OK;
+}
+extern "C++" {
+// launch(s) on the caller's stream, booked under the heads kind
+template <class Launch>
+static int heads_launch(ggnn_stream_t stream, Launch launch) {
+  Prof p(K_HEADS, (hipStream_t)stream);
+  launch(p.s);
+  LAUNCHCHK();
+  return GGNN_OK;
+}
+// how a pass with a workspace ends: decode_workspace for its need, then
+// launch(s, ws) with ws the caller's workspace, NULL when the pass asks for none
+template <class Launch>
+static int decode_launch(const char* name, size_t need, void* workspace, size_t workspace_bytes, ggnn_stream_t stream,
+                         Launch launch) {
+  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
+  return heads_launch(stream, [&](hipStream_t s) { launch(s, need ? workspace : nullptr); });
+}
+}  // extern "C++"
 
 // the heads' probabilities -> predicted (head, label) per node and the LAS /
 // UAS counts per graph (k_decode.h); booked under the heads kind
@@ -1711,19 +1744,16 @@ int ggnn_heads_decode(const ggnn_dims* d, const float* probs_head, int32_t o, co
                       int32_t* gold, int32_t* counts, ggnn_stream_t stream) {
   const bool null_arg = !probs_head || !probs_label || !n_nodes || !pred || !counts;
   if (int rc = decode_args("heads_decode", d, o, &oe, false, 0, null_arg)) return rc;
-  if ((gold_head == nullptr) != (gold_label == nullptr))
-    return fail(GGNN_EINVAL, "heads_decode: gold_head and gold_label must be given together (one is NULL)");
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
+  if (int rc = given_together("heads_decode", "gold_head", gold_head, "gold_label", gold_label)) return rc;
+  return heads_launch(stream, [&](hipStream_t s) {
 #define HDEC(NI_)                                                                                                  \
   hipLaunchKernelGGL(k_heads_decode<NI_>, dim3((unsigned)d->b), dim3(256), 0, s, probs_head, (int)o, probs_label,  \
                      (int)oe, gold_head, gold_label, (const int*)n_nodes, (int)d->v, (int*)pred,                   \
                      gold_head ? (int*)gold : nullptr, (int*)counts)
-  if (std::max(o, oe) <= 256) HDEC(4);
-  else HDEC(HEAD_MAXO / 64);
+    if (std::max(o, oe) <= 256) HDEC(4);
+    else HDEC(HEAD_MAXO / 64);
 #undef HDEC
-  LAUNCHCHK();
-  return GGNN_OK;
+  });
 }
 
 // the tree post-pass on ggnn_heads_decode's pred (k_tree.h); booked under the
@@ -1732,18 +1762,16 @@ static_assert(GGNN_TREE_MAXV == TREE_MAXV && GGNN_TREE_FORBIDDEN == TREE_FORBIDD
 size_t ggnn_tree_decode_workspace_bytes(int32_t, int32_t) { return 0; }
 int ggnn_tree_decode(const ggnn_dims* d, const int32_t* scores, int32_t o, const int32_t* n_nodes,
                      int32_t single_root, int32_t* pred, const int32_t* gold, int32_t* counts, int32_t* status,
-                     void* /*workspace*/, size_t /*workspace_bytes*/, ggnn_stream_t stream) {
-  if (int rc = decode_args("tree_decode", d, o, nullptr, true, single_root, !scores || !n_nodes || !pred || !status))
-    return rc;
-  if ((gold == nullptr) != (counts == nullptr))
-    return fail(GGNN_EINVAL, "tree_decode: gold and counts must be given together (one is NULL)");
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_tree_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
-                     (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
-                     (int*)status);
-  LAUNCHCHK();
-  return GGNN_OK;
+                     void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  const char* const name = "tree_decode";
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, !scores || !n_nodes || !pred || !status)) return rc;
+  if (int rc = given_together(name, "gold", gold, "counts", counts)) return rc;
+  const size_t need = ggnn_tree_decode_workspace_bytes(d->b, d->v);
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void*) {
+    hipLaunchKernelGGL(k_tree_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
+                       (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
+                       (int*)status);
+  });
 }
 
 // the projective post-pass on ggnn_heads_decode's pred (k_proj.h); booked under
@@ -1758,17 +1786,13 @@ int ggnn_projective_decode(const ggnn_dims* d, const int32_t* scores, int32_t o,
                            int32_t* status, void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
   const char* const name = "projective_decode";
   if (int rc = decode_args(name, d, o, nullptr, true, single_root, !scores || !n_nodes || !pred || !status)) return rc;
-  if ((gold == nullptr) != (counts == nullptr))
-    return fail(GGNN_EINVAL, "projective_decode: gold and counts must be given together (one is NULL)");
+  if (int rc = given_together(name, "gold", gold, "counts", counts)) return rc;
   const size_t need = ggnn_projective_decode_workspace_bytes(d->b, d->v);
-  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_projective_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
-                     (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
-                     (int*)status, need ? (int*)workspace : nullptr, (long)(2 * (long)d->v * (d->v + 1)));
-  LAUNCHCHK();
-  return GGNN_OK;
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void* ws) {
+    hipLaunchKernelGGL(k_projective_decode, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
+                       (const int*)n_nodes, (int)d->v, (int)single_root, (int*)pred, (const int*)gold, (int*)counts,
+                       (int*)status, (int*)ws, (long)(2 * (long)d->v * (d->v + 1)));
+  });
 }
 
 // projective arc marginals and the gather of the predicted heads' marginals
@@ -1787,26 +1811,21 @@ int ggnn_projective_marginals(const ggnn_dims* d, const float* probs_head, int32
   const char* const name = "projective_marginals";
   if (int rc = decode_args(name, d, o, nullptr, true, single_root, !probs_head || !n_nodes || !marg || !logz || !status))
     return rc;
-  if (marg == probs_head) return fail(GGNN_EINVAL, "projective_marginals: marg must not alias probs_head");
+  if (int rc = no_alias(name, marg, probs_head)) return rc;
   const size_t need = ggnn_projective_marginals_workspace_bytes(d->b, d->v);
-  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_projective_marginals, dim3((unsigned)d->b), dim3(256), 0, s, probs_head, (int)o,
-                     (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (int*)scores, (int*)status,
-                     need ? (float*)workspace : nullptr, (long)MARG_TABLES * PROJ_TRI((long)d->v));
-  LAUNCHCHK();
-  return GGNN_OK;
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void* ws) {
+    hipLaunchKernelGGL(k_projective_marginals, dim3((unsigned)d->b), dim3(256), 0, s, probs_head, (int)o,
+                       (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (int*)scores, (int*)status,
+                       (float*)ws, (long)MARG_TABLES * PROJ_TRI((long)d->v));
+  });
 }
 int ggnn_arc_confidence(const ggnn_dims* d, const float* marg, int32_t o, const int32_t* n_nodes,
                         const int32_t* pred, float* conf, ggnn_stream_t stream) {
   if (int rc = decode_args("arc_confidence", d, o, nullptr, false, 0, !marg || !n_nodes || !pred || !conf)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_arc_confidence, dim3(grid1d((long)d->b * d->v)), dim3(256), 0, s, marg, (int)o,
-                     (const int*)n_nodes, (int)d->b, (int)d->v, (const int*)pred, conf);
-  LAUNCHCHK();
-  return GGNN_OK;
+  return heads_launch(stream, [&](hipStream_t s) {
+    hipLaunchKernelGGL(k_arc_confidence, dim3(grid1d((long)d->b * d->v)), dim3(256), 0, s, marg, (int)o,
+                       (const int*)n_nodes, (int)d->b, (int)d->v, (const int*)pred, conf);
+  });
 }
 
 // arc marginals over all dependency trees (k_lapl.h); booked under the heads
@@ -1825,16 +1844,13 @@ int ggnn_tree_marginals(const ggnn_dims* d, const float* probs_head, int32_t o, 
   const char* const name = "tree_marginals";
   if (int rc = decode_args(name, d, o, nullptr, true, single_root, !probs_head || !n_nodes || !marg || !logz || !status))
     return rc;
-  if (marg == probs_head) return fail(GGNN_EINVAL, "tree_marginals: marg must not alias probs_head");
+  if (int rc = no_alias(name, marg, probs_head)) return rc;
   const size_t need = ggnn_tree_marginals_workspace_bytes(d->b, d->v);
-  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_tree_marginals, dim3((unsigned)d->b), dim3(LAPL_THREADS), 0, s, probs_head, (int)o,
-                     (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (int*)scores, (int*)status,
-                     need ? (float*)workspace : nullptr, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
-  LAUNCHCHK();
-  return GGNN_OK;
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void* ws) {
+    hipLaunchKernelGGL(k_tree_marginals, dim3((unsigned)d->b), dim3(LAPL_THREADS), 0, s, probs_head, (int)o,
+                       (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (int*)scores, (int*)status,
+                       (float*)ws, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
+  });
 }
 
 // the tree-structured training loss (k_tree_loss.h around the family's marginal
@@ -1856,34 +1872,29 @@ static int tree_loss_impl(const ggnn_dims* d, const float* probs_head, int32_t o
   if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
   if (family != 0 && family != 1) return fail(GGNN_EINVAL, "tree_loss: family must be 0 (all trees) or 1 (projective)");
   if (!tn_dev && !(target_num > 0.f)) return fail(GGNN_EINVAL, "tree_loss: target_num must be > 0");
-  if (marg == probs_head) return fail(GGNN_EINVAL, "tree_loss: marg must not alias probs_head");
+  if (int rc = no_alias(name, marg, probs_head)) return rc;
   const size_t need = ggnn_tree_loss_workspace_bytes(d->b, d->v, family);
   if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
   int* n_eff = (int*)workspace;
   const size_t head = tree_loss_head_bytes(d->b);
-  {
-    Prof p(K_HEADS, s);
+  if (int rc = heads_launch(stream, [&](hipStream_t s) {
 #define TLG(NI_)                                                                                                   \
   hipLaunchKernelGGL(k_tree_loss_gold<NI_>, dim3((unsigned)d->b), dim3(256), 0, s, gold_head, probs_head, (int)o, \
                      (const int*)n_nodes, (int)d->v, (int)family, (int)single_root, n_eff)
     if (o <= 256) TLG(4);
     else TLG(HEAD_MAXO / 64);
 #undef TLG
-    LAUNCHCHK();
-  }
+      }))
+    return rc;
   // the family's marginals over the eligible graphs (n_eff = 0: marg = probs, status 0)
   void* inner = need > head ? (void*)((char*)workspace + head) : nullptr;
   if (int rc = (family == 1 ? ggnn_projective_marginals : ggnn_tree_marginals)(
           d, probs_head, o, n_eff, single_root, marg, logz, nullptr, status, inner, need - head, stream))
     return rc;
-  {
-    Prof p(K_HEADS, s);
+  return heads_launch(stream, [&](hipStream_t s) {
     hipLaunchKernelGGL(k_tree_loss_fold, dim3(1), dim3(64), 0, s, (const int*)status, (const float*)logz, (int)d->b,
                        target_num, tn_dev, (int*)used, loss_inout);
-    LAUNCHCHK();
-  }
-  return GGNN_OK;
+  });
 }
 int ggnn_tree_loss(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
                    const int32_t* n_nodes, int32_t family, int32_t single_root, float target_num, float* marg,
@@ -1920,21 +1931,16 @@ int ggnn_tree_sample(const ggnn_dims* d, const float* probs_head, int32_t o, con
   const char* const name = "tree_sample";
   const bool null_arg = !probs_head || !n_nodes || !logz || !marg_status || !heads || !log_prob || !status;
   if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
-  if (num_samples < 1 || num_samples > GGNN_SAMPLE_MAX)
-    return fail(GGNN_EINVAL, "tree_sample: num_samples must lie in 1.." + std::to_string(GGNN_SAMPLE_MAX) + " (got " +
-                                 std::to_string(num_samples) + ")");
+  if (int rc = count_in_range(name, "num_samples", num_samples, GGNN_SAMPLE_MAX)) return rc;
   if (single_root && !marg) return fail(GGNN_EINVAL, "tree_sample: single_root needs marg (NULL pointer)");
-  if ((long)d->b * num_samples > 0x7FFFFFFFL) return fail(GGNN_EINVAL, "tree_sample: b * num_samples exceeds the grid");
+  if (int rc = fits_grid(name, "b * num_samples", (long)d->b * num_samples)) return rc;
   const size_t need = ggnn_tree_sample_workspace_bytes(d->b, d->v, num_samples);
-  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_tree_sample, dim3((unsigned)(d->b * num_samples)), dim3(LAPL_THREADS), 0, s, probs_head, (int)o,
-                     (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (const int*)marg_status,
-                     (int)num_samples, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob,
-                     (int*)status, need ? (float*)workspace : nullptr, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
-  LAUNCHCHK();
-  return GGNN_OK;
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void* ws) {
+    hipLaunchKernelGGL(k_tree_sample, dim3((unsigned)(d->b * num_samples)), dim3(LAPL_THREADS), 0, s, probs_head, (int)o,
+                       (const int*)n_nodes, (int)d->v, (int)single_root, marg, logz, (const int*)marg_status,
+                       (int)num_samples, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob,
+                       (int*)status, (float*)ws, (long)(d->v - 1) * LAPL_LD((long)d->v - 1));
+  });
 }
 
 // projective dependency trees drawn from the distribution of
@@ -1955,21 +1961,16 @@ int ggnn_projective_sample(const ggnn_dims* d, const float* probs_head, int32_t 
   const char* const name = "projective_sample";
   const bool null_arg = !probs_head || !n_nodes || !heads || !log_prob || !status;
   if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
-  if (num_samples < 1 || num_samples > GGNN_SAMPLE_MAX)
-    return fail(GGNN_EINVAL, "projective_sample: num_samples must lie in 1.." + std::to_string(GGNN_SAMPLE_MAX) +
-                                 " (got " + std::to_string(num_samples) + ")");
+  if (int rc = count_in_range(name, "num_samples", num_samples, GGNN_SAMPLE_MAX)) return rc;
   const long chunks = (long)proj_sample_chunks(num_samples);
-  if ((long)d->b * chunks > 0x7FFFFFFFL) return fail(GGNN_EINVAL, "projective_sample: b * chunks exceeds the grid");
+  if (int rc = fits_grid(name, "b * chunks", (long)d->b * chunks)) return rc;
   const size_t need = ggnn_projective_sample_workspace_bytes(d->b, d->v, num_samples);
-  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_projective_sample<PROJ_SAMPLE_CHUNK>, dim3((unsigned)(d->b * chunks)), dim3(256), 0, s, probs_head, (int)o,
-                     (const int*)n_nodes, (int)d->v, (int)single_root, (int)num_samples, (int)chunks,
-                     (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob, (int*)status, logz,
-                     need ? (float*)workspace : nullptr, (long)4 * PROJ_TRI((long)d->v));
-  LAUNCHCHK();
-  return GGNN_OK;
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void* ws) {
+    hipLaunchKernelGGL(k_projective_sample<PROJ_SAMPLE_CHUNK>, dim3((unsigned)(d->b * chunks)), dim3(256), 0, s,
+                       probs_head, (int)o, (const int*)n_nodes, (int)d->v, (int)single_root, (int)num_samples,
+                       (int)chunks, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (int*)heads, log_prob,
+                       (int*)status, logz, (float*)ws, (long)4 * PROJ_TRI((long)d->v));
+  });
 }
 
 // the K best projective trees of the integer head scores (k_proj_kbest.h);
@@ -1991,19 +1992,13 @@ int ggnn_projective_kbest(const ggnn_dims* d, const int32_t* scores, int32_t o, 
   const char* const name = "projective_kbest";
   const bool null_arg = !scores || !n_nodes || !heads || !totals || !count || !status;
   if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
-  if (K < 1 || K > GGNN_KBEST_MAX)
-    return fail(GGNN_EINVAL, "projective_kbest: K must lie in 1.." + std::to_string(GGNN_KBEST_MAX) + " (got " +
-                                 std::to_string(K) + ")");
+  if (int rc = count_in_range(name, "K", K, GGNN_KBEST_MAX)) return rc;
   const size_t need = ggnn_projective_kbest_workspace_bytes(d->b, d->v, K);
-  if (int rc = decode_workspace(name, need, workspace, workspace_bytes)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Prof p(K_HEADS, s);
-  hipLaunchKernelGGL(k_projective_kbest<256>, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
-                     (const int*)n_nodes, (int)d->v, (int)single_root, (int)K, (int*)heads, (int*)totals, (int*)count,
-                     (int*)status, need ? (int*)workspace : nullptr,
-                     (long)PROJ_TRI((long)d->v) * KBEST_SPAN_INTS((long)K));
-  LAUNCHCHK();
-  return GGNN_OK;
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void* ws) {
+    hipLaunchKernelGGL(k_projective_kbest<256>, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
+                       (const int*)n_nodes, (int)d->v, (int)single_root, (int)K, (int*)heads, (int*)totals, (int*)count,
+                       (int*)status, (int*)ws, (long)PROJ_TRI((long)d->v) * KBEST_SPAN_INTS((long)K));
+  });
 }
 
 }  // extern "C"

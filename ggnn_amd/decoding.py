@@ -69,6 +69,12 @@ def _as_np(t):
     return t.cpu().numpy() if isinstance(t, torch.Tensor) else t
 
 
+def _targets_rows(heads_row, labels_row, n):
+    """The JSON's 'targets' form [[head, label], ...] of nodes 1..n-1 (the label
+    one-based) from a graph's zero-based heads [v] and labels [v]."""
+    return [[int(h), int(l) + 1] for h, l in zip(heads_row[1:n], labels_row[1:n])]
+
+
 def _in_place(host_form):
     """A tree / projective pass with OutputHeads' signature over its host
     form: pred and counts are updated in place (the host form returns copies)."""
@@ -81,23 +87,26 @@ def _in_place(host_form):
     return run
 
 
+def _float32_marginals(host_form):
+    """A marginals pass with OutputHeads' signature over its host form: marg
+    and logz as float32, without the host form's span_max / cond."""
+    def run(self, probs_head, n_nodes, single_root=True, with_scores=True):
+        marg, logz, scores, status, _ = host_form(probs_head, n_nodes, single_root)
+        return marg.astype(np.float32), logz.astype(np.float32), scores if with_scores else None, status
+    return run
+
+
 class HostDecoder:
     """OutputHeads' nine decoding methods over the host forms, numpy in and
     out; the marginals as float32, without the host forms' span_max / cond /
     margin."""
     tree_decode = _in_place(_eval.tree_decode_arrays)
     projective_decode = _in_place(_eval.projective_decode_arrays)
+    projective_marginals = _float32_marginals(_eval.projective_marginals_arrays)
+    tree_marginals = _float32_marginals(_eval.tree_marginals_arrays)
 
     def decode(self, probs, n_nodes, labels=None):
         return _eval.decode_arrays(probs[0], probs[1], n_nodes, *(labels or (None, None)))
-
-    def projective_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True):
-        marg, logz, scores, status, _ = _eval.projective_marginals_arrays(probs_head, n_nodes, single_root)
-        return marg.astype(np.float32), logz.astype(np.float32), scores if with_scores else None, status
-
-    def tree_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True):
-        marg, logz, scores, status, _ = _eval.tree_marginals_arrays(probs_head, n_nodes, single_root)
-        return marg.astype(np.float32), logz.astype(np.float32), scores if with_scores else None, status
 
     def arc_confidence(self, marg, n_nodes, pred):
         return _eval.arc_confidence_arrays(marg, n_nodes, pred)
@@ -158,6 +167,7 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     sample_family = _sample_family(sample_family)
     on_device, family, confidence = isinstance(probs, torch.Tensor), _MBR_FAMILY.get(mode), _confidence_mode(confidence)
     marginals = lambda kind: backend.projective_marginals if kind == "projective" else backend.tree_marginals
+    head_scores = lambda: (tree_scores if on_device else _eval.tree_scores)(probs, n_nodes, probs.shape[1])
     pred, gold, counts = backend.decode([probs, probs_e], n_nodes, labels)
     regular = counts[:, 4] == 1
     n_reg = _select(regular, n_nodes, 0) if mode or confidence or samples or kbest else None
@@ -166,7 +176,7 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
         pred, gold, counts = backend.decode([marg, probs_e], n_nodes, labels)
         regular = regular & (has_marg == 1)
     elif mode:
-        scores = (tree_scores if on_device else _eval.tree_scores)(probs, n_nodes, probs.shape[1])
+        scores = head_scores()
     out = {"pred": pred, "gold": gold, "counts": counts, "tree_status": None}
     if mode:
         run = backend.tree_decode if mode in (True, "mbr") else backend.projective_decode
@@ -186,7 +196,7 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
         out["sample_status"] = _select(counts[:, 4:5] == 1, status, 2)
     if kbest:
         if family or not mode:       # (the chain's scores are the marginals', or there are none)
-            scores = (tree_scores if on_device else _eval.tree_scores)(probs, n_nodes, probs.shape[1])
+            scores = head_scores()
         out["kbest_heads"], out["kbest_total"], out["kbest_count"], status = backend.projective_kbest(
             scores, n_reg, kbest, single_root)
         out["kbest_status"] = _select(counts[:, 4] == 1, status, 2)
@@ -340,12 +350,8 @@ class DecodingMixin:
         nothing; anything outside 0..KBEST_MAX is a ValueError."""
         tree = _tree_mode(tree, confidence, "predict_batch")
         sample_family = _sample_family(sample_family)
-        samples = int(samples)
-        if not 0 <= samples <= _eval.SAMPLE_MAX:
-            raise ValueError("samples must lie in 0..%d (got %d)" % (_eval.SAMPLE_MAX, samples))
-        kbest = int(kbest)
-        if not 0 <= kbest <= _eval.KBEST_MAX:
-            raise ValueError("kbest must lie in 0..%d (got %d)" % (_eval.KBEST_MAX, kbest))
+        samples = _eval._count_in_range("samples", samples, _eval.SAMPLE_MAX, 0)
+        kbest = _eval._count_in_range("kbest", kbest, _eval.KBEST_MAX, 0)
         r = self._decode_forward(feed_dict, False, tree, single_root, confidence, samples, sample_seed, sample_family,
                                  kbest)
         ph, b, v, pred = r["ph"], r["b"], r["v"], r["pred"]
@@ -355,35 +361,38 @@ class DecodingMixin:
                         / self.output_size_edges).astype(np.int32)
         else:
             n, pred = r["n_nodes"], _as_np(pred)
-        status = _as_np(r["tree_status"])
-        if tree and status is None:          # masks not in closed form: the repair is not attempted
-            status = np.full(b, 2, np.int32)
         out = {"heads": np.ascontiguousarray(pred[:, :, 0]), "labels": np.ascontiguousarray(pred[:, :, 1]),
-               "n_nodes": n, "sentences_id": ph.get("sentences_id"), "tree_status": status}
-        if confidence:
-            conf, logz = r["head_confidence"], r["log_partition"]
-            if conf is None:                 # masks not in closed form: no marginals
-                conf, logz = np.zeros((b, v), np.float32), np.full(b, np.nan, np.float32)
-            out["head_confidence"], out["log_partition"] = _as_np(conf), _as_np(logz)
-        if samples:
-            if r.get("sampled_heads") is None:      # masks not in closed form: not attempted
-                r["sampled_heads"] = np.full((b, samples, v), -1, np.int32)
-                r["sample_log_prob"] = np.full((b, samples), -np.inf, np.float32)
-                r["sample_status"] = np.full((b, samples), 2, np.int32)
-            for k in ("sampled_heads", "sample_log_prob", "sample_status"):
-                out[k] = _as_np(r[k])
+               "n_nodes": n, "sentences_id": ph.get("sentences_id"), "tree_status": None}
+        # what the chain adds: (the keyword that asks for it, key, shape, dtype, the value where nothing was
+        # attempted -- masks not in closed form: no repair, no marginals, no samples, no k-best)
+        for asked, key, shape, dtype, fill in ((tree, "tree_status", (b,), np.int32, 2),
+                                               (confidence, "head_confidence", (b, v), np.float32, 0),
+                                               (confidence, "log_partition", (b,), np.float32, np.nan),
+                                               (samples, "sampled_heads", (b, samples, v), np.int32, -1),
+                                               (samples, "sample_log_prob", (b, samples), np.float32, -np.inf),
+                                               (samples, "sample_status", (b, samples), np.int32, 2),
+                                               (kbest, "kbest_heads", (b, kbest, v), np.int32, -1),
+                                               (kbest, "kbest_count", (b,), np.int32, 0),
+                                               (kbest, "kbest_status", (b,), np.int32, 2),
+                                               (kbest, "kbest_total", (b, kbest), np.int32, _eval.TREE_FORBIDDEN)):
+            if asked:
+                out[key] = np.full(shape, fill, dtype) if r.get(key) is None else _as_np(r[key])
         if kbest:
-            if r.get("kbest_heads") is None:        # masks not in closed form: not attempted
-                r["kbest_heads"] = np.full((b, kbest, v), -1, np.int32)
-                r["kbest_total"] = np.full((b, kbest), _eval.TREE_FORBIDDEN, np.int32)
-                r["kbest_count"], r["kbest_status"] = np.zeros(b, np.int32), np.full(b, 2, np.int32)
-            for k in ("kbest_heads", "kbest_count", "kbest_status"):
-                out[k] = _as_np(r[k])
-            total = _as_np(r["kbest_total"]).astype(np.float64)
+            total = out.pop("kbest_total").astype(np.float64)
             present = np.arange(kbest)[None, :] < out["kbest_count"][:, None]
             scale = np.log(2.0) / 2.0 ** _eval.tree_score_shift(v)
             out["kbest_log_prob"] = np.where(present, total * scale, -np.inf).astype(np.float32)
         return out
+
+    def _predict_raw(self, raw_data, *args, seed=0, **kwargs):
+        """predict_batch(feed, *args, **kwargs) over the batches of raw btb
+        sentences, as (batch number, result) pairs.  The sentences are copied
+        ('targets' may be absent) and carry their input position as 'id', so
+        a result's 'sentences_id' index raw_data.  Batch number i draws its
+        samples, if any, with sample_seed (seed + i) mod 2^64."""
+        raw = [{"targets": [], **d, "id": k} for k, d in enumerate(raw_data)]
+        for i, feed in enumerate(self.make_minibatch_iterator(self.process_raw_graphs(raw, False), False)):
+            yield i, self.predict_batch(feed, *args, sample_seed=(int(seed) + i) % 2 ** 64, **kwargs)
 
     def parse_kbest(self, raw_data, k, single_root=True):
         """The k best projective dependency trees of raw btb sentences
@@ -394,15 +403,12 @@ class DecodingMixin:
         each one's 'kbest_log_prob', aligned and non-increasing.  A sentence
         with fewer than k projective trees yields those it has; a sentence
         process_raw_graphs drops yields []."""
-        raw = [{"targets": [], **d, "id": i} for i, d in enumerate(raw_data)]
-        out, log_probs = [[] for _ in raw], [[] for _ in raw]
-        data = self.process_raw_graphs(raw, False)
-        for feed in self.make_minibatch_iterator(data, False):
-            p = self.predict_batch(feed, False, single_root, kbest=k)
+        raw_data = list(raw_data)
+        out, log_probs = [[] for _ in raw_data], [[] for _ in raw_data]
+        for _, p in self._predict_raw(raw_data, False, single_root, kbest=k):
             for g, s in enumerate(p["sentences_id"]):
-                n = int(p["n_nodes"][g])
                 for r in range(int(p["kbest_count"][g])):
-                    out[s].append([[int(h), int(l) + 1] for h, l in zip(p["kbest_heads"][g, r, 1:n], p["labels"][g, 1:n])])
+                    out[s].append(_targets_rows(p["kbest_heads"][g, r], p["labels"][g], int(p["n_nodes"][g])))
                     log_probs[s].append(float(p["kbest_log_prob"][g, r]))
         return out, log_probs
 
@@ -420,17 +426,13 @@ class DecodingMixin:
         trees.  family="projective": the trees are drawn from the distribution
         over projective trees (predict_batch(sample_family="projective"))."""
         family = _sample_family(family)
-        raw = [{"targets": [], **d, "id": k} for k, d in enumerate(raw_data)]
-        out, log_probs = [[] for _ in raw], [[] for _ in raw]
-        data = self.process_raw_graphs(raw, False)
-        for i, feed in enumerate(self.make_minibatch_iterator(data, False)):
-            p = self.predict_batch(feed, False, single_root, samples=num_samples,
-                                   sample_seed=(int(seed) + i) % 2 ** 64, sample_family=family)
+        raw_data = list(raw_data)
+        out, log_probs = [[] for _ in raw_data], [[] for _ in raw_data]
+        for _, p in self._predict_raw(raw_data, False, single_root, samples=num_samples, sample_family=family,
+                                      seed=seed):
             for g, k in enumerate(p["sentences_id"]):
-                n = int(p["n_nodes"][g])
                 for s in np.nonzero(p["sample_status"][g] == 1)[0]:
-                    out[k].append([[int(h), int(l) + 1] for h, l in zip(p["sampled_heads"][g, s, 1:n],
-                                                                        p["labels"][g, 1:n])])
+                    out[k].append(_targets_rows(p["sampled_heads"][g, s], p["labels"][g], int(p["n_nodes"][g])))
                     log_probs[k].append(float(p["sample_log_prob"][g, s]))
         return out, log_probs
 
@@ -453,12 +455,9 @@ class DecodingMixin:
         with tree=True or "mbr"), "nonprojective" under the one over all
         dependency trees (every value of tree)."""
         tree = _tree_mode(tree, confidence, "parse")
-        # (copies: the batches carry the input position as 'id')
-        raw = [{"targets": [], **d, "id": k} for k, d in enumerate(raw_data)]
-        out, conf = [[] for _ in raw], [[] for _ in raw]
-        data = self.process_raw_graphs(raw, False)
-        for feed in self.make_minibatch_iterator(data, False):
-            p = self.predict_batch(feed, tree, single_root, confidence)
+        raw_data = list(raw_data)
+        out, conf = [[] for _ in raw_data], [[] for _ in raw_data]
+        for _, p in self._predict_raw(raw_data, tree, single_root, confidence):
             for g, (k, heads, labels) in enumerate(zip(p["sentences_id"], p["heads"], p["labels"])):
                 rg_h = [[int(x), 1] for x in heads[1:] if x >= 0]
                 rg_e = [[0, int(x) + 1] for x in labels[1:] if x >= 0]

@@ -173,6 +173,29 @@ def _node_counts(n_nodes, b, v, o):
     return n
 
 
+def _count_in_range(name, x, top, low=1):
+    """int(x) for a count (K, num_samples; low 0: predict_batch's samples /
+    kbest, 0 = off) that must lie in low..top."""
+    x = int(x)
+    if not low <= x <= top:
+        raise ValueError("%s must lie in %d..%d (got %d)" % (name, low, top, x))
+    return x
+
+
+def _head_input(x, n_nodes, name, dtype, what):
+    """How the host forms of the tree passes open: x as a [b, v, o] array
+    (``name`` in the messages; int32 scores must come as int32, probabilities
+    are converted to float32), the shape rule the kernels share (``what``
+    opens its message) and _node_counts.  Returns (array, b, v, o, nn)."""
+    a = np.asarray(x) if dtype == np.int32 else np.asarray(x, dtype)
+    if a.ndim != 3 or a.dtype != dtype:
+        raise ValueError("%s must be %s[b, v, o]" % (name, "int32 " if dtype == np.int32 else ""))
+    b, v, o = a.shape
+    if v > o or v > TREE_MAXV or o > 1024:
+        raise ValueError("%s v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (what, TREE_MAXV, v, o))
+    return a, b, v, o, _node_counts(n_nodes, b, v, o)
+
+
 def decode_arrays(probs, probs_e, n_nodes, labels=None, labels_e=None):
     """The host form of ``ggnn_heads_decode`` (include/ggnn.h), written with
     the scorer's own ``_first_max``: probs [b, v, o] and probs_e [b, v, e] are
@@ -470,12 +493,7 @@ def _repair_arrays(what, fine, solve, scores, n_nodes, pred, gold, counts):
     recount.  ``fine(scores[g], n, heads)``: the graph's heads are left alone
     (status 0); else ``solve(scores[g], n)`` gives its new heads (status 1) or
     None (status 2)."""
-    s = np.asarray(scores)
-    if s.ndim != 3 or s.dtype != np.int32:
-        raise ValueError("scores must be int32 [b, v, o]")
-    b, v, o = s.shape
-    if v > o or v > TREE_MAXV or o > 1024:
-        raise ValueError("%s decode needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (what, TREE_MAXV, v, o))
+    s, b, v, o, nn = _head_input(scores, n_nodes, "scores", np.int32, what + " decode needs")
     pred = np.array(pred, np.int32)
     if pred.shape != (b, v, 2):
         raise ValueError("pred must be [%d, %d, 2]" % (b, v))
@@ -484,7 +502,6 @@ def _repair_arrays(what, fine, solve, scores, n_nodes, pred, gold, counts):
     if counts is not None:
         counts = np.array(counts, np.int32)
         gold = np.asarray(gold)
-    nn = _node_counts(n_nodes, b, v, o)
     status = np.zeros(b, np.int32)
     for g in range(b):
         n = int(nn[g])
@@ -550,6 +567,16 @@ def is_projective(heads, n):
 
 def _proj_add(a, b):
     return np.where((a == _PROJ_NEG) | (b == _PROJ_NEG), _PROJ_NEG, a + b)
+
+
+def _range_ok(scores_g, n):
+    """The range rule of the integer span programmes: S * (n - 1) < 2^30 for
+    the largest absolute allowed score S of the graph's n nodes (no total
+    then reaches _PROJ_NEG)."""
+    a = scores_g[1:n, :n].astype(np.int64)
+    live = a != TREE_FORBIDDEN
+    live[np.arange(n - 1), np.arange(1, n)] = False
+    return int(np.abs(a[live]).max(initial=0)) * (n - 1) < 2 ** 30
 
 
 def _eisner(s, n, single_root):
@@ -636,17 +663,10 @@ def projective_decode_arrays(scores, n_nodes, pred, single_root=True, gold=None,
     uas recounted; status 0 = already a projective tree (or n < 2), 2 = S *
     (n - 1) >= 2^30 for the largest absolute allowed score S, or no projective
     tree exists; those graphs are returned as passed in."""
-    def solve(sg, n):
-        a = sg[1:n, :n].astype(np.int64)
-        live = a != TREE_FORBIDDEN
-        live[np.arange(n - 1), np.arange(1, n)] = False
-        if int(np.abs(a[live]).max(initial=0)) * (n - 1) >= 2 ** 30:      # the range rule
-            return None
-        return _eisner(sg, n, single_root)
-
     return _repair_arrays("projective",
                           lambda sg, n, heads: is_tree(heads, n, single_root, sg) and is_projective(heads, n),
-                          solve, scores, n_nodes, pred, gold, counts)
+                          lambda sg, n: _eisner(sg, n, single_root) if _range_ok(sg, n) else None,
+                          scores, n_nodes, pred, gold, counts)
 
 
 def random_projective_heads(n, rng):
@@ -788,16 +808,8 @@ def projective_kbest_arrays(scores, n_nodes, K, single_root=True):
     < 2, 1 = count >= 1, 2 = S * (n - 1) >= 2^30 for the largest absolute
     allowed score S, or no projective tree exists).  Rank 0 is _eisner's tree,
     ties included; the list for K is a prefix of the list for a larger K."""
-    s = np.asarray(scores)
-    if s.ndim != 3 or s.dtype != np.int32:
-        raise ValueError("scores must be int32 [b, v, o]")
-    b, v, o = s.shape
-    if v > o or v > TREE_MAXV or o > 1024:
-        raise ValueError("projective k-best needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
-    K = int(K)
-    if not 1 <= K <= KBEST_MAX:
-        raise ValueError("K must lie in 1..%d (got %d)" % (KBEST_MAX, K))
-    nn = _node_counts(n_nodes, b, v, o)
+    s, b, v, o, nn = _head_input(scores, n_nodes, "scores", np.int32, "projective k-best needs")
+    K = _count_in_range("K", K, KBEST_MAX)
     heads = np.full((b, K, v), -1, np.int32)
     totals = np.full((b, K), TREE_FORBIDDEN, np.int32)
     count, status = np.zeros(b, np.int32), np.zeros(b, np.int32)
@@ -806,10 +818,7 @@ def projective_kbest_arrays(scores, n_nodes, K, single_root=True):
         if n < 2:
             continue
         status[g] = 2
-        a = s[g, 1:n, :n].astype(np.int64)
-        live = a != TREE_FORBIDDEN
-        live[np.arange(n - 1), np.arange(1, n)] = False
-        if int(np.abs(a[live]).max(initial=0)) * (n - 1) >= 2 ** 30:      # the range rule
+        if not _range_ok(s[g], n):
             continue
         _, backs, fv, fb = _kbest_tables(s[g], n, bool(single_root), K)
         c = int((fv != _PROJ_NEG).sum())
@@ -945,6 +954,17 @@ def _inside_outside(psi, n, single_root):
     return logz, np.minimum(marg, 1).astype(dt), span_max
 
 
+def _marginals_out(marg, scores, g, n, ok, mg):
+    """Graph g's written marginals, for both marginals forms: mg [n, n] on the
+    allowed arcs ``ok`` and 0 elsewhere into marg[g]; rint(marg * 2^20) of the
+    float32 marginals on the allowed arcs into scores[g] (TREE_FORBIDDEN
+    elsewhere, as it was filled)."""
+    marg[g] = 0
+    marg[g, :n, :n] = np.where(ok, mg, 0)
+    scores[g, :n, :n] = np.where(ok, np.rint(marg[g, :n, :n].astype(np.float32) * np.float32(MARG_SCORE_SCALE)),
+                                 TREE_FORBIDDEN).astype(np.int32)
+
+
 def projective_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.float64):
     """The host form of ``ggnn_projective_marginals`` (include/ggnn.h):
     probs_head float32 [b, v, o], n_nodes [b].  The potential of "word i takes
@@ -961,14 +981,8 @@ def projective_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.
     absolute finite value of the inside and outside tables and of logz
     (float; what an fp32 kernel's stored values are rounded at).  The tables
     are kept in ``dtype``."""
-    p = np.asarray(probs_head, np.float32)
-    if p.ndim != 3:
-        raise ValueError("probs_head must be [b, v, o]")
-    b, v, o = p.shape
-    if v > o or v > TREE_MAXV or o > 1024:
-        raise ValueError("projective marginals need v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    p, b, v, o, nn = _head_input(probs_head, n_nodes, "probs_head", np.float32, "projective marginals need")
     dt = np.dtype(dtype)
-    nn = _node_counts(n_nodes, b, v, o)
     marg = p.astype(dt)
     logz = np.zeros(b, dt)
     scores = np.full((b, v, o), TREE_FORBIDDEN, np.int32)
@@ -985,10 +999,7 @@ def projective_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.
             status[g] = 2
             continue
         status[g] = 1
-        marg[g] = 0
-        marg[g, :n, :n] = np.where(ok, mg, 0)
-        scores[g, :n, :n] = np.where(ok, np.rint(marg[g, :n, :n].astype(np.float32) * np.float32(MARG_SCORE_SCALE)),
-                                     TREE_FORBIDDEN).astype(np.int32)
+        _marginals_out(marg, scores, g, n, ok, mg)
     return marg, logz, scores, status, span_max
 
 
@@ -1084,15 +1095,9 @@ def tree_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.float6
     cond[g]: the 1-norm condition number of the graph's normalised matrix in
     float64 (1 for n < 3, inf for status 2): an elimination in fp32 is off by
     about n * cond * 2^-24.  Matrix, inverse and determinant in ``dtype``."""
-    p = np.asarray(probs_head, np.float32)
-    if p.ndim != 3:
-        raise ValueError("probs_head must be [b, v, o]")
-    b, v, o = p.shape
-    if v > o or v > TREE_MAXV or o > 1024:
-        raise ValueError("tree marginals need v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
+    p, b, v, o, nn = _head_input(probs_head, n_nodes, "probs_head", np.float32, "tree marginals need")
     dt = np.dtype(dtype)
     single_root = bool(single_root)
-    nn = _node_counts(n_nodes, b, v, o)
     marg = p.astype(dt)
     logz = np.zeros(b, dt)
     scores = np.full((b, v, o), TREE_FORBIDDEN, np.int32)
@@ -1130,10 +1135,7 @@ def tree_marginals_arrays(probs_head, n_nodes, single_root=True, dtype=np.float6
                                                       single_root), 1))
         else:
             cond[g] = 1.0
-        marg[g] = 0
-        marg[g, :n, :n] = np.where(ok, np.clip(mg, 0, 1), 0)
-        scores[g, :n, :n] = np.where(ok, np.rint(marg[g, :n, :n].astype(np.float32) * np.float32(MARG_SCORE_SCALE)),
-                                     TREE_FORBIDDEN).astype(np.int32)
+        _marginals_out(marg, scores, g, n, ok, np.clip(mg, 0, 1))
     return marg, logz, scores, status, cond
 
 
@@ -1305,17 +1307,12 @@ def tree_sample_arrays(probs_head, n_nodes, num_samples, seed, single_root=True,
     place of the draws; log_prob is then the sum of the logs of the
     conditional probabilities met (-inf where one is 0: not a tree of the
     distribution) and heads returns them.  Matrix and updates in ``dtype``."""
-    p = np.asarray(probs_head, np.float32)
-    if p.ndim != 3:
-        raise ValueError("probs_head must be [b, v, o]")
-    b, v, o = p.shape
-    K = int(num_samples)
-    if not 1 <= K <= SAMPLE_MAX:
-        raise ValueError("num_samples must lie in 1..%d (got %d)" % (SAMPLE_MAX, K))
+    # (the shape rule in the words of tree_marginals_arrays, which runs below)
+    p, b, v, o, nn = _head_input(probs_head, n_nodes, "probs_head", np.float32, "tree marginals need")
+    K = _count_in_range("num_samples", num_samples, SAMPLE_MAX)
     dt = np.dtype(dtype)
     single_root = bool(single_root)
     marg, logz, _, m_status, _ = tree_marginals_arrays(p, n_nodes, single_root, dt)
-    nn = _node_counts(n_nodes, b, v, o)
     if forced is not None:
         forced = np.asarray(forced, np.int64)
         if forced.ndim == 2:
@@ -1539,19 +1536,11 @@ def projective_sample_arrays(probs_head, n_nodes, num_samples, seed, single_root
     draws; log_prob is then the sum of the logs of the conditional
     probabilities met (-inf for a head vector that is no projective tree of
     the distribution) and heads returns them.  Tables in ``dtype``."""
-    p = np.asarray(probs_head, np.float32)
-    if p.ndim != 3:
-        raise ValueError("probs_head must be [b, v, o]")
-    b, v, o = p.shape
-    if v > o or v > TREE_MAXV or o > 1024:
-        raise ValueError("projective sampling needs v <= o, v <= %d, o <= 1024 (got v %d, o %d)" % (TREE_MAXV, v, o))
-    K = int(num_samples)
-    if not 1 <= K <= SAMPLE_MAX:
-        raise ValueError("num_samples must lie in 1..%d (got %d)" % (SAMPLE_MAX, K))
+    p, b, v, o, nn = _head_input(probs_head, n_nodes, "probs_head", np.float32, "projective sampling needs")
+    K = _count_in_range("num_samples", num_samples, SAMPLE_MAX)
     dt = np.dtype(dtype)
     single_root = bool(single_root)
     lo = 1 if single_root else 0
-    nn = _node_counts(n_nodes, b, v, o)
     if forced is not None:
         forced = np.asarray(forced, np.int64)
         if forced.ndim == 2:

@@ -24,7 +24,8 @@ import torch
 from .upload import Uploader
 
 from . import _lib
-from .evaluation import TREE_LOG2_FLOOR, tree_score_shift  # noqa: F401  (tree_score_shift: re-exported)
+from .evaluation import TREE_LOG2_FLOOR, _count_in_range
+from .evaluation import tree_score_shift  # noqa: F401  (tree_score_shift: re-exported)
 
 SMALL_NUMBER = 1e-7   # utils.py
 
@@ -174,14 +175,10 @@ class OutputHeads:
         self.hidden = int(hidden)
         self._lib = _lib.load()
         self._ws = None
-        self._tree_ws = None   # ggnn_tree_decode's workspace (the kernel asks for none today)
-        self._proj_ws = None   # ggnn_projective_decode's workspace (graphs above PROJ_LDS_MAXN nodes)
-        self._marg_ws = None   # ggnn_projective_marginals' workspace (graphs above MARG_LDS_MAXN nodes)
-        self._lapl_ws = None   # ggnn_tree_marginals' workspace (graphs above LAPL_LDS_MAXN nodes)
-        self._sample_ws = None  # ggnn_tree_sample's workspace (graphs above SAMPLE_LDS_MAXN nodes)
-        self._proj_sample_ws = None  # ggnn_projective_sample's workspace (graphs above PROJ_SAMPLE_LDS_MAXN nodes)
-        self._kbest_ws = None  # ggnn_projective_kbest's workspace (graphs above ggnn_projective_kbest_lds_maxn(K) nodes)
-        self._loss_ws = None   # ggnn_tree_loss' workspace (n_eff, then the family's marginals workspace)
+        # pass name -> the binding's own workspace for ggnn_<name> (_pass): only
+        # for graphs above the pass's *_LDS_MAXN nodes (tree_decode asks for none
+        # today; tree_loss always: n_eff, then the family's marginals workspace)
+        self._pass_ws = {}
         self._saved = None
         # the last forward's structured loss (tree_loss=): the marginals that
         # stand in head 0's probs place in the backward, and used int32 [b];
@@ -257,33 +254,23 @@ class OutputHeads:
         heads' backward takes in the probabilities' place), any other graph's
         a copy of probs_head.  workspace: a uint8 tensor to use instead of the
         binding's own."""
-        _check_tensor(probs_head, "probs_head", torch.float32)
         family = {"nonprojective": 0, "projective": 1}.get(family, family)
         if family not in (0, 1):
             raise ValueError("family must be 0 / 'nonprojective' or 1 / 'projective'")
-        b, v, o = probs_head.shape
-        dev = probs_head.device
-        if v > o or v > _lib.TREE_MAXV:
-            raise ValueError("tree_loss needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
+        b, v, o, dev, run = self._pass("tree_loss", probs_head, "probs_head", torch.float32, n_nodes, workspace, family)
         _check_tensor(gold_head, "gold_head", torch.float32)
         if gold_head.shape != probs_head.shape or gold_head.device != dev:
             raise ValueError("gold_head must have probs_head's shape and device")
-        _check_n_nodes(n_nodes, b, dev)
         if loss.dtype != torch.float32 or loss.device != dev or loss.numel() < 1 or not loss.is_contiguous():
             raise ValueError("loss must be a contiguous float32 tensor on %s" % dev)
-        need = int(self._lib.ggnn_tree_loss_workspace_bytes(b, v, family))
-        workspace = self._workspace("_loss_ws", need, dev, workspace)
         marg = torch.empty_like(probs_head)
         logz = torch.empty(b, dtype=torch.float32, device=dev)
         status = torch.empty(b, dtype=torch.int32, device=dev)
         used = torch.empty(b, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
         on_dev = isinstance(target_num, torch.Tensor)
-        fn = self._lib.ggnn_tree_loss_dev if on_dev else self._lib.ggnn_tree_loss
-        _lib.check(fn(ctypes.byref(d), _ptr(probs_head), o, _ptr(gold_head), _ptr(n_nodes), int(family),
-                      int(bool(single_root)), _ptr(target_num) if on_dev else float(target_num), _ptr(marg),
-                      _ptr(logz), _ptr(status), _ptr(used), _ptr(loss), _ptr(workspace), workspace.numel(), _stream()),
-                   "ggnn_tree_loss_dev" if on_dev else "ggnn_tree_loss")
+        run(_ptr(gold_head), _ptr(n_nodes), int(family), int(bool(single_root)),
+            _ptr(target_num) if on_dev else float(target_num), _ptr(marg), _ptr(logz), _ptr(status), _ptr(used),
+            _ptr(loss), entry="tree_loss_dev" if on_dev else "tree_loss")
         return marg, logz, status, used
 
     def backward(self, hT, h0, heads, labels, probs, target_num=1.0, d_loss=None, dws=None, dbs=None, dhT=None,
@@ -345,15 +332,14 @@ class OutputHeads:
                    "ggnn_heads_decode")
         return pred, gold, counts
 
-    def _workspace(self, attr, need, dev, workspace=None):
-        """A pass's workspace of ``need`` bytes: the binding's own buffer
-        ``attr``, grown on demand (None when the pass asks for none), or the
+    def _workspace(self, name, need, dev, workspace=None):
+        """Pass ``name``'s workspace of ``need`` bytes: the binding's own
+        buffer, grown on demand (None when the pass asks for none), or the
         caller's once it is checked."""
         if workspace is None:
-            own = getattr(self, attr)
+            own = self._pass_ws.get(name)
             if need and (own is None or own.numel() < need or own.device != dev):
-                own = torch.empty(need, dtype=torch.uint8, device=dev)
-                setattr(self, attr, own)
+                own = self._pass_ws[name] = torch.empty(need, dtype=torch.uint8, device=dev)
             return own if need else None
         if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
             raise ValueError("workspace must be a contiguous uint8 tensor on %s" % dev)
@@ -361,29 +347,41 @@ class OutputHeads:
             raise ValueError("workspace of %d bytes, %d needed" % (workspace.numel(), need))
         return workspace
 
-    def _tree_pass(self, name, attr, scores, n_nodes, pred, gold, counts, single_root, workspace=None):
-        """tree_decode / projective_decode: ggnn_<name> with its workspace."""
-        _check_tensor(scores, "scores", torch.int32)
-        b, v, o = scores.shape
-        dev = scores.device
+    def _pass(self, name, x, x_name, dtype, n_nodes, workspace, *size_args):
+        """What the passes with a workspace share, either side of a pass's own
+        part.  Before it: the checks of the input ``x`` (``dtype`` [b, v, o]
+        on the GPU, ``x_name`` in the messages), of the shape rule and of
+        n_nodes.  Returns (b, v, o, device, run).  After it: ``run(*middle)``
+        sizes the workspace (ggnn_<name>_workspace_bytes(b, v, *size_args);
+        the binding's own buffer or the caller's ``workspace``) and calls
+        ggnn_<name>(dims, x, o, *middle, workspace, its bytes, stream);
+        ``entry``: another entry point with that signature and size."""
+        _check_tensor(x, x_name, dtype)
+        b, v, o = x.shape
+        dev = x.device
         if v > o or v > _lib.TREE_MAXV:
             raise ValueError("%s needs v <= o and v <= %d (got v %d, o %d)" % (name, _lib.TREE_MAXV, v, o))
         _check_n_nodes(n_nodes, b, dev)
+
+        def run(*middle, entry=name):
+            need = int(getattr(self._lib, "ggnn_%s_workspace_bytes" % name)(b, v, *size_args))
+            ws = self._workspace(name, need, dev, workspace)
+            d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
+            _lib.check(getattr(self._lib, "ggnn_" + entry)(ctypes.byref(d), _ptr(x), o, *middle, _ptr(ws),
+                                                           0 if ws is None else ws.numel(), _stream()), "ggnn_" + entry)
+        return b, v, o, dev, run
+
+    def _tree_pass(self, name, scores, n_nodes, pred, gold, counts, single_root, workspace=None):
+        """tree_decode / projective_decode: ggnn_<name> with its workspace."""
+        b, v, o, dev, run = self._pass(name, scores, "scores", torch.int32, n_nodes, workspace)
         if (gold is None) != (counts is None):
             raise ValueError("gold and counts are given together")
         _check_int32(pred, "pred", (b, v, 2), dev)
         if gold is not None:
             _check_int32(gold, "gold", (b, v, 2), dev)
             _check_int32(counts, "counts", (b, _lib.DECODE_COUNTS), dev)
-        need = int(getattr(self._lib, "ggnn_%s_workspace_bytes" % name)(b, v))
-        workspace = self._workspace(attr, need, dev, workspace)
         status = torch.empty(b, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(getattr(self._lib, "ggnn_" + name)(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes),
-                                                      int(bool(single_root)), _ptr(pred), _ptr(gold), _ptr(counts),
-                                                      _ptr(status), _ptr(workspace),
-                                                      0 if workspace is None else workspace.numel(), _stream()),
-                   "ggnn_" + name)
+        run(_ptr(n_nodes), int(bool(single_root)), _ptr(pred), _ptr(gold), _ptr(counts), _ptr(status))
         return status
 
     def tree_decode(self, scores, n_nodes, pred, gold=None, counts=None, single_root=True):
@@ -395,7 +393,7 @@ class OutputHeads:
         status int32 [b]: 0 = pred's heads already were a tree, 1 = replaced
         by the maximum spanning tree of the scores, 2 = no tree exists (the
         graph is left as it was)."""
-        return self._tree_pass("tree_decode", "_tree_ws", scores, n_nodes, pred, gold, counts, single_root)
+        return self._tree_pass("tree_decode", scores, n_nodes, pred, gold, counts, single_root)
 
     def projective_decode(self, scores, n_nodes, pred, gold=None, counts=None, single_root=True, workspace=None):
         """The projective post-pass on ``decode``'s pred, on the same stream
@@ -405,30 +403,17 @@ class OutputHeads:
         projective tree exists or the scores are out of range (the graph is
         left as it was).  workspace: a uint8 tensor to use instead of the
         binding's own (grown on demand; needed for v > PROJ_LDS_MAXN only)."""
-        return self._tree_pass("projective_decode", "_proj_ws", scores, n_nodes, pred, gold, counts, single_root,
-                               workspace)
+        return self._tree_pass("projective_decode", scores, n_nodes, pred, gold, counts, single_root, workspace)
 
-    def _marginals_pass(self, name, attr, p, n_nodes, single_root, with_scores, workspace):
+    def _marginals_pass(self, name, p, n_nodes, single_root, with_scores, workspace):
         """projective_marginals / tree_marginals: ggnn_<name> with its outputs
         and its workspace."""
-        _check_tensor(p, "probs_head", torch.float32)
-        b, v, o = p.shape
-        dev = p.device
-        if v > o or v > _lib.TREE_MAXV:
-            raise ValueError("%s needs v <= o and v <= %d (got v %d, o %d)" % (name, _lib.TREE_MAXV, v, o))
-        _check_n_nodes(n_nodes, b, dev)
-        need = int(getattr(self._lib, "ggnn_%s_workspace_bytes" % name)(b, v))
-        workspace = self._workspace(attr, need, dev, workspace)
+        b, v, o, dev, run = self._pass(name, p, "probs_head", torch.float32, n_nodes, workspace)
         marg = torch.empty_like(p)
         logz = torch.empty(b, dtype=torch.float32, device=dev)
         scores = torch.empty(b, v, o, dtype=torch.int32, device=dev) if with_scores else None
         status = torch.empty(b, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(getattr(self._lib, "ggnn_" + name)(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes),
-                                                      int(bool(single_root)), _ptr(marg), _ptr(logz), _ptr(scores),
-                                                      _ptr(status), _ptr(workspace),
-                                                      0 if workspace is None else workspace.numel(), _stream()),
-                   "ggnn_" + name)
+        run(_ptr(n_nodes), int(bool(single_root)), _ptr(marg), _ptr(logz), _ptr(scores), _ptr(status))
         return marg, logz, scores, status
 
     def projective_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True, workspace=None):
@@ -442,8 +427,7 @@ class OutputHeads:
         and scores are all forbidden).  workspace: a uint8 tensor to use
         instead of the binding's own (grown on demand; needed for v >
         MARG_LDS_MAXN only)."""
-        return self._marginals_pass("projective_marginals", "_marg_ws", probs_head, n_nodes, single_root, with_scores,
-                                    workspace)
+        return self._marginals_pass("projective_marginals", probs_head, n_nodes, single_root, with_scores, workspace)
 
     def tree_marginals(self, probs_head, n_nodes, single_root=True, with_scores=True, workspace=None):
         """The posterior marginal of every arc under the distribution over ALL
@@ -454,8 +438,7 @@ class OutputHeads:
         tree exists; ``tree_decode`` on the scores gives the minimum Bayes
         risk tree.  workspace: a uint8 tensor to use instead of the binding's
         own (grown on demand; needed for v > LAPL_LDS_MAXN only)."""
-        return self._marginals_pass("tree_marginals", "_lapl_ws", probs_head, n_nodes, single_root, with_scores,
-                                    workspace)
+        return self._marginals_pass("tree_marginals", probs_head, n_nodes, single_root, with_scores, workspace)
 
     def tree_sample(self, probs_head, n_nodes, num_samples, seed=0, single_root=True, marginals=None, workspace=None):
         """num_samples dependency trees per graph drawn from the distribution
@@ -471,16 +454,8 @@ class OutputHeads:
         = n < 2, 2 = no tree exists or a numerical dead end).  workspace: a
         uint8 tensor to use instead of the binding's own (grown on demand;
         needed for v > SAMPLE_LDS_MAXN only)."""
-        p = probs_head
-        _check_tensor(p, "probs_head", torch.float32)
-        b, v, o = p.shape
-        dev = p.device
-        if v > o or v > _lib.TREE_MAXV:
-            raise ValueError("tree_sample needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
-        K = int(num_samples)
-        if not 1 <= K <= _lib.SAMPLE_MAX:
-            raise ValueError("num_samples must lie in 1..%d (got %d)" % (_lib.SAMPLE_MAX, K))
-        _check_n_nodes(n_nodes, b, dev)
+        p, K = probs_head, _count_in_range("num_samples", num_samples, _lib.SAMPLE_MAX)
+        b, v, o, dev, run = self._pass("tree_sample", p, "probs_head", torch.float32, n_nodes, workspace, K)
         if marginals is None:
             marginals = self.tree_marginals(p, n_nodes, single_root, with_scores=False)
         marg, logz, _, m_status = marginals
@@ -488,18 +463,11 @@ class OutputHeads:
                 or logz.dtype != torch.float32 or logz.device != dev or logz.numel() != b or not logz.is_contiguous()):
             raise ValueError("marginals must be tree_marginals' outputs for probs_head")
         _check_int32(m_status, "marginals' status", (b,), dev)
-        need = int(self._lib.ggnn_tree_sample_workspace_bytes(b, v, K))
-        workspace = self._workspace("_sample_ws", need, dev, workspace)
         heads = torch.empty(b, K, v, dtype=torch.int32, device=dev)
         log_prob = torch.empty(b, K, dtype=torch.float32, device=dev)
         status = torch.empty(b, K, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(self._lib.ggnn_tree_sample(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes), int(bool(single_root)),
-                                              _ptr(marg), _ptr(logz), _ptr(m_status), K,
-                                              int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(heads), _ptr(log_prob),
-                                              _ptr(status), _ptr(workspace),
-                                              0 if workspace is None else workspace.numel(), _stream()),
-                   "ggnn_tree_sample")
+        run(_ptr(n_nodes), int(bool(single_root)), _ptr(marg), _ptr(logz), _ptr(m_status), K,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(heads), _ptr(log_prob), _ptr(status))
         return heads, log_prob, status
 
     def projective_sample(self, probs_head, n_nodes, num_samples, seed=0, single_root=True, workspace=None):
@@ -517,28 +485,15 @@ class OutputHeads:
         ``projective_marginals``' ln Z).  workspace: a uint8 tensor to use
         instead of the binding's own (grown on demand; needed for v >
         PROJ_SAMPLE_LDS_MAXN only)."""
-        p = probs_head
-        _check_tensor(p, "probs_head", torch.float32)
-        b, v, o = p.shape
-        dev = p.device
-        if v > o or v > _lib.TREE_MAXV:
-            raise ValueError("projective_sample needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
-        K = int(num_samples)
-        if not 1 <= K <= _lib.SAMPLE_MAX:
-            raise ValueError("num_samples must lie in 1..%d (got %d)" % (_lib.SAMPLE_MAX, K))
-        _check_n_nodes(n_nodes, b, dev)
-        need = int(self._lib.ggnn_projective_sample_workspace_bytes(b, v, K))
-        workspace = self._workspace("_proj_sample_ws", need, dev, workspace)
+        K = _count_in_range("num_samples", num_samples, _lib.SAMPLE_MAX)
+        b, v, o, dev, run = self._pass("projective_sample", probs_head, "probs_head", torch.float32, n_nodes,
+                                       workspace, K)
         heads = torch.empty(b, K, v, dtype=torch.int32, device=dev)
         log_prob = torch.empty(b, K, dtype=torch.float32, device=dev)
         status = torch.empty(b, K, dtype=torch.int32, device=dev)
         logz = torch.empty(b, dtype=torch.float32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(self._lib.ggnn_projective_sample(ctypes.byref(d), _ptr(p), o, _ptr(n_nodes), int(bool(single_root)),
-                                                    K, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(heads), _ptr(log_prob),
-                                                    _ptr(status), _ptr(logz), _ptr(workspace),
-                                                    0 if workspace is None else workspace.numel(), _stream()),
-                   "ggnn_projective_sample")
+        run(_ptr(n_nodes), int(bool(single_root)), K, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(heads), _ptr(log_prob),
+            _ptr(status), _ptr(logz))
         return heads, log_prob, status, logz
 
     def projective_kbest(self, scores, n_nodes, K, single_root=True, workspace=None):
@@ -555,27 +510,13 @@ class OutputHeads:
         the scores are out of range).  workspace: a uint8 tensor to use instead
         of the binding's own (grown on demand; needed for v >
         ggnn_projective_kbest_lds_maxn(K) only)."""
-        _check_tensor(scores, "scores", torch.int32)
-        b, v, o = scores.shape
-        dev = scores.device
-        if v > o or v > _lib.TREE_MAXV:
-            raise ValueError("projective_kbest needs v <= o and v <= %d (got v %d, o %d)" % (_lib.TREE_MAXV, v, o))
-        K = int(K)
-        if not 1 <= K <= _lib.KBEST_MAX:
-            raise ValueError("K must lie in 1..%d (got %d)" % (_lib.KBEST_MAX, K))
-        _check_n_nodes(n_nodes, b, dev)
-        need = int(self._lib.ggnn_projective_kbest_workspace_bytes(b, v, K))
-        workspace = self._workspace("_kbest_ws", need, dev, workspace)
+        K = _count_in_range("K", K, _lib.KBEST_MAX)
+        b, v, o, dev, run = self._pass("projective_kbest", scores, "scores", torch.int32, n_nodes, workspace, K)
         heads = torch.empty(b, K, v, dtype=torch.int32, device=dev)
         totals = torch.empty(b, K, dtype=torch.int32, device=dev)
         count = torch.empty(b, dtype=torch.int32, device=dev)
         status = torch.empty(b, dtype=torch.int32, device=dev)
-        d = _lib.dims(b, v, self.hidden, 1, 1, True, "fp32")
-        _lib.check(self._lib.ggnn_projective_kbest(ctypes.byref(d), _ptr(scores), o, _ptr(n_nodes),
-                                                   int(bool(single_root)), K, _ptr(heads), _ptr(totals), _ptr(count),
-                                                   _ptr(status), _ptr(workspace),
-                                                   0 if workspace is None else workspace.numel(), _stream()),
-                   "ggnn_projective_kbest")
+        run(_ptr(n_nodes), int(bool(single_root)), K, _ptr(heads), _ptr(totals), _ptr(count), _ptr(status))
         return heads, totals, count, status
 
     def arc_confidence(self, marg, n_nodes, pred):

@@ -137,6 +137,124 @@ def test_heads_decode_rejects_bad_arguments_without_gpu(lib):
     assert "ggnn_heads_decode" in _lib.EXPORTED and _lib.DECODE_COUNTS == 5
 
 
+def _abi_entries(lib):
+    """{entry: call(**changes)} for the decode entry points of the C ABI at b = 2,
+    v = 20, o = 150 with dummy pointers (no call here gets past validation):
+    x everywhere, y where a pointer must differ from the input."""
+    import ctypes
+    from ggnn_amd import _lib
+    x, y = ctypes.c_void_p(256), ctypes.c_void_p(512)
+    tail = ("ws", "ws_bytes", "stream")
+    a_pass = ("x", "o", "n", "single", "pred", "gold", "counts", "status") + tail
+    marginals = ("x", "o", "n", "single", "marg", "logz", "scores", "status") + tail
+    loss = ("x", "o", "gold_head", "n", "family", "single", "tn", "marg", "logz", "status", "used", "loss") + tail
+    order = {"heads_decode": ("x", "o", "pl", "oe", "gh", "gl", "n", "pred", "gold", "counts", "stream"),
+             "tree_decode": a_pass, "projective_decode": a_pass,
+             "projective_marginals": marginals, "tree_marginals": marginals,
+             "arc_confidence": ("x", "o", "n", "pred", "conf", "stream"),
+             "tree_loss": loss, "tree_loss_dev": loss,
+             "tree_sample": ("x", "o", "n", "single", "marg", "logz", "m_status", "num", "seed", "heads", "log_prob",
+                             "status") + tail,
+             "projective_sample": ("x", "o", "n", "single", "num", "seed", "heads", "log_prob", "status",
+                                   "logz") + tail,
+             "projective_kbest": ("x", "o", "n", "single", "K", "heads", "totals", "count", "status") + tail}
+    ok = dict(dims=True, b=2, v=20, o=150, oe=12, single=1, family=0, num=3, K=3, seed=0, ws=None, ws_bytes=0,
+              stream=None, gh=None, gl=None, gold=None, counts=None, marg=y)
+
+    def entry(name):
+        def call(**changes):
+            a = dict(ok, **changes)
+            if name.startswith("tree_loss"):        # the loss entries always take a workspace
+                a = dict(dict(ok, ws=x, ws_bytes=1 << 40, tn=x if name.endswith("_dev") else 1.0), **changes)
+            elif name == "heads_decode":
+                a = dict(dict(ok, counts=x), **changes)
+            d = _lib.dims(a["b"], a["v"], 64, 1, 1)
+            args = [a.get(k, x) for k in order[name]]
+            rc = getattr(lib, "ggnn_" + name)(ctypes.byref(d) if a["dims"] else None, *args)
+            return rc, lib.ggnn_last_error()
+        return call
+    return {name: entry(name) for name in order}, x
+
+
+def test_abi_reports_the_first_fault_in_the_documented_order(lib):
+    """Two faults in one call: every decode entry point reports the one that
+    comes first in dims, b / v, o, v > o, GGNN_TREE_MAXV, single_root, NULL, the
+    entry's own checks (in its own order), workspace -- with these exact texts."""
+    calls, x = _abi_entries(lib)
+    together = lambda name: "%s: gold and counts must be given together (one is NULL)" % name
+    alias = lambda name: "%s: marg must not alias probs_head" % name
+    count = lambda name, what, top, got: "%s: %s must lie in 1..%d (got %d)" % (name, what, top, got)
+    grid = lambda name, what: "%s: %s exceeds the grid" % (name, what)
+    # entry -> (a required pointer, [(faults of its own checks in order, the text)], v of a short workspace)
+    tree_passes = {
+        "tree_decode": ("pred", [(dict(gold=x), together("tree_decode"))], None),
+        "projective_decode": ("status", [(dict(counts=x), together("projective_decode"))], 129),
+        "projective_marginals": ("logz", [(dict(marg=x), alias("projective_marginals"))], 108),
+        "tree_marginals": ("n", [(dict(marg=x), alias("tree_marginals"))], 200),
+        "tree_loss": ("used", [(dict(family=2), "tree_loss: family must be 0 (all trees) or 1 (projective)"),
+                               (dict(tn=0.0), "tree_loss: target_num must be > 0"),
+                               (dict(marg=x), alias("tree_loss"))], 20),
+        "tree_loss_dev": ("ws", [(dict(family=-1), "tree_loss: family must be 0 (all trees) or 1 (projective)"),
+                                 (dict(marg=x), alias("tree_loss"))], 20),
+        "tree_sample": ("m_status", [(dict(num=0), count("tree_sample", "num_samples", 4096, 0)),
+                                     (dict(marg=None), "tree_sample: single_root needs marg (NULL pointer)"),
+                                     (dict(b=1 << 20, num=4096), grid("tree_sample", "b * num_samples"))], 200),
+        "projective_sample": ("log_prob", [(dict(num=4097), count("projective_sample", "num_samples", 4096, 4097)),
+                                           (dict(b=1 << 23, num=4096), grid("projective_sample", "b * chunks"))],
+                              129),
+        "projective_kbest": ("totals", [(dict(K=17), count("projective_kbest", "K", 16, 17))],
+                             lib.ggnn_projective_kbest_lds_maxn(3) + 1)}
+    cases = []
+    for name, (ptr, own, v_short) in tree_passes.items():
+        said = "tree_loss" if name == "tree_loss_dev" else name
+        first, last = own[0], own[-1]
+        cases += [(name, dict(dims=False, b=0), "%s: dims is NULL" % said),
+                  (name, dict(b=0, o=0), "%s: b, v must be >= 1" % said),
+                  (name, dict(v=0, o=1025), "%s: b, v must be >= 1" % said),
+                  (name, dict(o=0), "%s: o must lie in 1..1024 (got 0)" % said),
+                  (name, dict(v=257, o=256), "%s: v 257 > o 256" % said),
+                  (name, {"o": 19, ptr: None}, "%s: v 20 > o 19" % said),
+                  (name, dict(v=257, o=300, single=2), "%s: v 257 > GGNN_TREE_MAXV 256" % said),
+                  (name, {"single": 2, ptr: None}, "%s: single_root must be 0 or 1" % said),
+                  (name, dict(first[0], single=-1), "%s: single_root must be 0 or 1" % said),
+                  (name, {ptr: None, **first[0]}, "%s: NULL pointer" % said)]
+        cases += [(name, dict(later[0], **earlier[0]), earlier[1]) for earlier, later in zip(own, own[1:])]
+        if v_short:                                  # the last own check beside a workspace that is too short
+            cases.append((name, dict(last[0], v=v_short, o=256, ws=None if v_short > 20 else x, ws_bytes=0), last[1]))
+    cases += [("tree_loss_dev", dict(tn=None, dims=False), "tree_loss_dev: NULL target_num"),
+              ("tree_sample", dict(num=0, marg=None, b=1 << 20), count("tree_sample", "num_samples", 4096, 0)),
+              ("projective_sample", dict(num=0, v=129, o=256), count("projective_sample", "num_samples", 4096, 0)),
+              ("arc_confidence", dict(dims=False, v=0), "arc_confidence: dims is NULL"),
+              ("arc_confidence", dict(b=0, o=0), "arc_confidence: b, v must be >= 1"),
+              ("arc_confidence", dict(o=1025, v=0), "arc_confidence: b, v must be >= 1"),
+              ("arc_confidence", dict(o=0), "arc_confidence: o must lie in 1..1024 (got 0)"),
+              ("arc_confidence", dict(o=19, conf=None), "arc_confidence: v 20 > o 19"),
+              ("arc_confidence", dict(v=257, o=300, pred=None), "arc_confidence: NULL pointer"),
+              ("heads_decode", dict(dims=False, o=0), "heads_decode: dims is NULL"),
+              ("heads_decode", dict(b=0, oe=0), "heads_decode: b, v must be >= 1"),
+              ("heads_decode", dict(o=0), "heads_decode: o and oe must lie in 1..1024 (got 0, 12)"),
+              ("heads_decode", dict(oe=1025, o=19), "heads_decode: o and oe must lie in 1..1024 (got 19, 1025)"),
+              ("heads_decode", dict(o=19, pl=None), "heads_decode: v 20 > o 19"),
+              ("heads_decode", dict(v=257, o=300, counts=None, gh=x), "heads_decode: NULL pointer"),
+              ("heads_decode", dict(gl=x),
+               "heads_decode: gold_head and gold_label must be given together (one is NULL)")]
+    # a short workspace alone: the last report, with the size the entry's own query gives
+    for name, size, v in (("projective_decode", lib.ggnn_projective_decode_workspace_bytes(2, 129), 129),
+                          ("projective_marginals", lib.ggnn_projective_marginals_workspace_bytes(2, 108), 108),
+                          ("tree_marginals", lib.ggnn_tree_marginals_workspace_bytes(2, 200), 200),
+                          ("tree_sample", lib.ggnn_tree_sample_workspace_bytes(2, 200, 3), 200),
+                          ("projective_sample", lib.ggnn_projective_sample_workspace_bytes(2, 129, 3), 129)):
+        assert size > 0
+        cases.append((name, dict(v=v, o=256), "%s: workspace of 0 bytes, %d needed" % (name, size)))
+        cases.append((name, dict(v=v, o=256, ws=x, ws_bytes=size - 1),
+                      "%s: workspace of %d bytes, %d needed" % (name, size - 1, size)))
+    cases.append(("tree_loss", dict(ws_bytes=255), "tree_loss: workspace of 255 bytes, 256 needed"))
+    assert len(cases) > 120 and {name for name, _, _ in cases} == set(calls)
+    for name, changes, text in cases:
+        rc, said = calls[name](**changes)
+        assert rc == -1 and said == text.encode(), (name, changes, said)
+
+
 def test_real_dev_gold_lists_are_regular():
     """The first 40 dev sentences (tests/test_gpu_decode.py scores them on the
     device): every real node has a gold head and label, so with non-zero
@@ -303,6 +421,91 @@ def test_score_epoch_equals_run_epoch_on_a_cpu_device():
     # the shared epoch loop's progress line changes no value
     loud = m.run_epoch("valid", data, False, verbose=True)
     assert (loud[0], loud[4], loud[5], loud[6], loud[16]) == (ref[0], ref[4], ref[5], ref[6], ref[16])
+
+
+def test_predict_batch_without_closed_form_masks_attempts_nothing():
+    """A feed whose masks the decode cannot rebuild: heads / labels come from
+    the feed's own masks and every structured key holds its "not attempted"
+    value, in the shapes and dtypes of a decoded batch."""
+    m = _stub_forward(_cpu_model(4), decimals=2)
+    feed = dict(next(iter(m.make_minibatch_iterator(m.process_raw_graphs(_raw(), False), False))))
+    b, v, o, oe = feed["num_graphs"], feed["num_vertices"], m.params["output_size"], m.output_size_edges
+    assert b == 2
+    mask = np.array(feed["node_mask"], dtype=np.float64)
+    mask.reshape(-1)[0] = 0.5                         # not get_mask's closed form: no node counts
+    feed["node_mask"] = mask
+    assert m._feed_n_nodes(feed) is None
+    p = m.predict_batch(feed, tree="projective", confidence=True, samples=3, kbest=2)
+    assert list(p) == ["heads", "labels", "n_nodes", "sentences_id", "tree_status", "head_confidence",
+                       "log_partition", "sampled_heads", "sample_log_prob", "sample_status", "kbest_heads",
+                       "kbest_count", "kbest_status", "kbest_log_prob"]
+    pred = E.pred_from_masks(m.ops["computed_values"].numpy(), m.ops["computed_values_edges"].numpy(),
+                             mask.astype(np.float32).reshape(b, v, o),
+                             np.asarray(feed["node_mask_edges"], np.float32).reshape(b, v, oe))
+    n = np.asarray(feed["node_mask_edges"]).reshape(b, -1).sum(axis=1) / oe
+    want = {"heads": (pred[:, :, 0], np.int32), "labels": (pred[:, :, 1], np.int32), "n_nodes": (n, np.int32),
+            "tree_status": (np.full(b, 2), np.int32),
+            "head_confidence": (np.zeros((b, v)), np.float32), "log_partition": (np.full(b, np.nan), np.float32),
+            "sampled_heads": (np.full((b, 3, v), -1), np.int32),
+            "sample_log_prob": (np.full((b, 3), -np.inf), np.float32), "sample_status": (np.full((b, 3), 2), np.int32),
+            "kbest_heads": (np.full((b, 2, v), -1), np.int32), "kbest_count": (np.zeros(b), np.int32),
+            "kbest_status": (np.full(b, 2), np.int32), "kbest_log_prob": (np.full((b, 2), -np.inf), np.float32)}
+    for key, (value, dtype) in want.items():
+        assert isinstance(p[key], np.ndarray) and p[key].dtype == dtype and p[key].shape == value.shape, key
+        assert np.array_equal(p[key], value, equal_nan=True), key
+    assert list(p["sentences_id"]) == list(feed["sentences_id"])
+    assert (p["heads"][:, 1:] >= 0).any()
+    for kw, text in ((dict(samples=E.SAMPLE_MAX + 1), "samples must lie in 0..4096 (got 4097)"),
+                     (dict(samples=-1), "samples must lie in 0..4096 (got -1)"),
+                     (dict(kbest=E.KBEST_MAX + 1), "kbest must lie in 0..16 (got 17)"),
+                     (dict(kbest=-1), "kbest must lie in 0..16 (got -1)")):
+        with pytest.raises(ValueError) as err:
+            m.predict_batch(feed, **kw)
+        assert str(err.value) == text
+
+
+def test_raw_sentence_drivers_equal_predict_batch_per_batch():
+    """parse, parse_kbest and sample_trees are predict_batch over the batches
+    of the raw sentences: the lists land at the input positions, and batch i
+    of sample_trees draws with seed (seed + i) mod 2^64."""
+    m = _stub_forward(_cpu_model(5), decimals=2)
+    raw = _raw()
+    feeds = list(m.make_minibatch_iterator(m.process_raw_graphs([dict(d, id=i) for i, d in enumerate(raw)], False),
+                                           False))
+    assert len(feeds) >= 5
+    assert [s for f in feeds for s in f["sentences_id"]] != sorted(s for f in feeds for s in f["sentences_id"])
+
+    def expected(rows, **kw):
+        """[per input sentence: what rows(p, g, n) lists] over predict_batch(feed, **kw(i)) of batch i."""
+        out = [[] for _ in raw]
+        for i, feed in enumerate(feeds):
+            p = m.predict_batch(feed, **{k: x(i) if callable(x) else x for k, x in kw.items()})
+            for g, s in enumerate(p["sentences_id"]):
+                out[s] = rows(p, g, int(p["n_nodes"][g]))
+        return out
+
+    pairs = lambda heads, p, g, n: [[int(h), int(lab) + 1] for h, lab in zip(heads[1:n], p["labels"][g, 1:n])]
+    assert m.parse(raw) == expected(lambda p, g, n: pairs(p["heads"][g], p, g, n))
+    trees, conf = m.parse(raw, tree="projective", confidence=True)
+    assert trees == expected(lambda p, g, n: pairs(p["heads"][g], p, g, n), tree="projective")
+    assert conf == expected(lambda p, g, n: [float(c) for c in p["head_confidence"][g, 1:n]], tree="projective",
+                            confidence=True)
+    ranks = lambda p, g: range(int(p["kbest_count"][g]))
+    trees, log_probs = m.parse_kbest(raw, 2)
+    assert trees == expected(lambda p, g, n: [pairs(p["kbest_heads"][g, r], p, g, n) for r in ranks(p, g)], kbest=2)
+    assert log_probs == expected(lambda p, g, n: [float(p["kbest_log_prob"][g, r]) for r in ranks(p, g)], kbest=2)
+    assert max(map(len, trees)) == 2 and trees[5] == [] == log_probs[5]          # (the empty sentence)
+    drawn = lambda p, g: np.nonzero(p["sample_status"][g] == 1)[0]
+    for family in ("nonprojective", "projective"):
+        for seed in (5, 2 ** 64 - 2):                # (the second: batches 2.. wrap round to seeds 0..)
+            kw = dict(samples=2, sample_family=family, sample_seed=lambda i: (seed + i) % 2 ** 64)
+            trees, log_probs = m.sample_trees(raw, 2, seed=seed, family=family)
+            assert trees == expected(lambda p, g, n: [pairs(p["sampled_heads"][g, s], p, g, n) for s in drawn(p, g)],
+                                     **kw), (family, seed)
+            assert log_probs == expected(lambda p, g, n: [float(p["sample_log_prob"][g, s]) for s in drawn(p, g)],
+                                         **kw), (family, seed)
+            assert sum(map(len, trees)) == 2 * (len(raw) - 1)
+    assert m.sample_trees(raw, 2, seed=5)[0] != m.sample_trees(raw, 2, seed=6)[0]
 
 
 def test_host_decoder_and_output_heads_take_the_same_arguments():
