@@ -40,6 +40,7 @@ EXPORTED = (
     "ggnn_tree_sample_workspace_bytes", "ggnn_tree_sample",
     "ggnn_projective_sample_workspace_bytes", "ggnn_projective_sample",
     "ggnn_projective_kbest_lds_maxn", "ggnn_projective_kbest_workspace_bytes", "ggnn_projective_kbest",
+    "ggnn_tree_kbest_workspace_bytes", "ggnn_tree_kbest",
 )
 DECODE_COUNTS = 5   # include/ggnn.h GGNN_DECODE_COUNTS: n_kept, las, uas, lab, regular
 TREE_MAXV = 256                # include/ggnn.h GGNN_TREE_MAXV
@@ -153,7 +154,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
                                     ("projective_marginals", 0, [_P] * 4), ("tree_marginals", 0, [_P] * 4),
                                     ("tree_sample", 1, [_P, _P, _P, I32, U64, _P, _P, _P]),
                                     ("projective_sample", 1, [I32, U64, _P, _P, _P, _P]),
-                                    ("projective_kbest", 1, [I32, _P, _P, _P, _P])):
+                                    ("projective_kbest", 1, [I32, _P, _P, _P, _P]),
+                                    ("tree_kbest", 1, [I32, _P, _P, _P, _P])):
             size, entry = getattr(lib, "ggnn_%s_workspace_bytes" % name), getattr(lib, "ggnn_" + name)
             size.restype, size.argtypes = ctypes.c_size_t, [I32] * (2 + sized)
             entry.restype, entry.argtypes = _I, [_DP, _P, I32, _P, I32] + middle + [_P, ctypes.c_size_t, _P]

@@ -33,6 +33,7 @@
 #include "k_tree_sample.h"
 #include "k_proj_sample.h"
 #include "k_proj_kbest.h"
+#include "k_tree_kbest.h"
 
 // ---------------------------------------------------------------------------
 // error handling (thread-local last error; no exception crosses the ABI)
@@ -1998,6 +1999,36 @@ int ggnn_projective_kbest(const ggnn_dims* d, const int32_t* scores, int32_t o, 
     hipLaunchKernelGGL(k_projective_kbest<256>, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
                        (const int*)n_nodes, (int)d->v, (int)single_root, (int)K, (int*)heads, (int*)totals, (int*)count,
                        (int*)status, (int*)ws, (long)PROJ_TRI((long)d->v) * KBEST_SPAN_INTS((long)K));
+  });
+}
+
+// the K best trees over all dependency trees of the integer head scores
+// (k_tree_kbest.h): take(0), then solve(r - 1), take(r) for every further rank;
+// booked under the heads kind
+size_t ggnn_tree_kbest_workspace_bytes(int32_t b, int32_t v, int32_t K) {
+  if (b < 1 || v < 1 || K < 1 || K > GGNN_KBEST_MAX) return 0;
+  return (size_t)b * sizeof(int32_t) * (size_t)TKB_STRIDE((size_t)v, (size_t)K);
+}
+int ggnn_tree_kbest(const ggnn_dims* d, const int32_t* scores, int32_t o, const int32_t* n_nodes, int32_t single_root,
+                    int32_t K, int32_t* heads, int32_t* totals, int32_t* count, int32_t* status, void* workspace,
+                    size_t workspace_bytes, ggnn_stream_t stream) {
+  const char* const name = "tree_kbest";
+  const bool null_arg = !scores || !n_nodes || !heads || !totals || !count || !status;
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
+  if (int rc = count_in_range(name, "K", K, GGNN_KBEST_MAX)) return rc;
+  if (int rc = fits_grid(name, "b * (v - 1)", (long)d->b * (d->v - 1))) return rc;
+  const size_t need = ggnn_tree_kbest_workspace_bytes(d->b, d->v, K);
+  return decode_launch(name, need, workspace, workspace_bytes, stream, [&](hipStream_t s, void* ws) {
+    const long stride = TKB_STRIDE((long)d->v, (long)K);
+    for (int r = 0; r < K; ++r) {
+      hipLaunchKernelGGL(k_tree_kbest_take<256>, dim3((unsigned)d->b), dim3(256), 0, s, (const int*)scores, (int)o,
+                         (const int*)n_nodes, (int)d->v, (int)single_root, (int)K, r, (int*)heads, (int*)totals,
+                         (int*)count, (int*)status, (int*)ws, stride);
+      if (r + 1 < K && d->v > 1)
+        hipLaunchKernelGGL(k_tree_kbest_solve<256>, dim3((unsigned)(d->b * (d->v - 1))), dim3(256), 0, s,
+                           (const int*)scores, (int)o, (const int*)n_nodes, (int)d->v, (int)single_root, (int)K, r,
+                           (const int*)heads, (int*)ws, stride);
+    }
   });
 }
 

@@ -36,6 +36,10 @@
 // 2n steps of expansion.  One workgroup of 256 threads per graph, no atomics,
 // no inter-workgroup communication; all choices are "first wins" in index
 // order, so two launches give the same bytes.
+//
+// The contraction and the expansion are tree_solve, which reads an arc's score
+// through an accessor: k_tree_decode gives it the graph's own scores,
+// k_tree_kbest.h the scores under a subproblem's mask.
 #pragma once
 #include "ggnn_common.h"
 
@@ -104,38 +108,39 @@ DEV void tree_recount(const int* __restrict__ gold, int* __restrict__ counts, co
   }
 }
 
-// scores [b][v][o], n_nodes [b], pred [b][v][2] in/out, gold [b][v][2] and
-// counts [b][DECODE_COUNTS] both or neither, status [b].  grid = b, block = 256.
-__global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ scores, int o,
-                                                     const int* __restrict__ n_nodes, int v, int single_root,
-                                                     int* __restrict__ pred, const int* __restrict__ gold,
-                                                     int* __restrict__ counts, int* __restrict__ status) {
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = tree_node_count(n_nodes[g], v, o);
-  const long base = (long)g * v;
-  const int* __restrict__ S = scores + base * o;
-  if (n < 2) {
-    if (tid == 0) status[g] = 0;
-    return;
-  }
-  const int K = tree_doublings(n);
-
+// ---- the solver, shared by k_tree_decode and k_tree_kbest.h.  Its state in
+// LDS (28 KiB: a kernel declares one __shared__ TreeSolve):
+struct TreeSolve {
   // per word
-  __shared__ int label[TREE_MAXV], dirty[TREE_MAXV], wsrc[TREE_MAXV], nh[TREE_MAXV];
-  __shared__ long long off[TREE_MAXV], wval[TREE_MAXV];
+  int label[TREE_MAXV], dirty[TREE_MAXV], wsrc[TREE_MAXV], nh[TREE_MAXV];
+  long long off[TREE_MAXV], wval[TREE_MAXV];
   // per forest node (words 0..n-1, contracted cycles n..2n-3)
-  __shared__ int tpar[2 * TREE_MAXV], in_u[2 * TREE_MAXV], in_i[2 * TREE_MAXV], jp[2 * TREE_MAXV],
-      jm[2 * TREE_MAXV], oncyc[2 * TREE_MAXV], newid[2 * TREE_MAXV], entered[2 * TREE_MAXV];
-  __shared__ long long bestv[2 * TREE_MAXV];
-  __shared__ int wcnt[8];
+  int tpar[2 * TREE_MAXV], in_u[2 * TREE_MAXV], in_i[2 * TREE_MAXV], jp[2 * TREE_MAXV], jm[2 * TREE_MAXV],
+      oncyc[2 * TREE_MAXV], newid[2 * TREE_MAXV], entered[2 * TREE_MAXV];
+  long long bestv[2 * TREE_MAXV];
+  int wcnt[8];
+};
+// an arc's score as the solver reads it: score(i, j) for word i and head j
+// below n, TREE_FORBIDDEN = no such arc.  The graph's own scores:
+struct TreePlainScores {
+  const int* __restrict__ S;
+  int o;
+  DEV int operator()(int i, int j) const { return S[(long)i * o + j]; }
+};
 
-  // ---- the fast path: pred's heads already are a tree
-  TreePred t = tree_pred_arc(pred, S, o, base, n, jp, tid);
-  tree_pred_follow(t, n, K, jp, tid);
-  if (t.is_tree && (!single_root || t.roots == 1)) {
-    if (tid == 0) status[g] = 0;
-    return;
-  }
+// Rounds A-D and the expansion on the graph whose arcs `score` gives (n >= 2
+// nodes, K = tree_doublings(n)).  Called by the whole workgroup of 256 threads
+// with the same arguments; true: sh.nh[1 .. n-1] hold the heads of a maximum
+// arborescence (with single_root: of one ROOT child), false: no such tree
+// exists.  The answer is the same in every thread, and the true return follows
+// a barrier after the last write of sh.nh.
+template <class Score>
+DEV bool tree_solve(TreeSolve& sh, const Score& score, int n, int K, int single_root, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  int *const label = sh.label, *const dirty = sh.dirty, *const wsrc = sh.wsrc, *const nh = sh.nh;
+  long long *const off = sh.off, *const wval = sh.wval, *const bestv = sh.bestv;
+  int *const tpar = sh.tpar, *const in_u = sh.in_u, *const in_i = sh.in_i, *const jp = sh.jp, *const jm = sh.jm,
+             *const oncyc = sh.oncyc, *const newid = sh.newid, *const entered = sh.entered, *const wcnt = sh.wcnt;
 
   // ---- Chu-Liu/Edmonds
   for (int x = tid; x < 2 * TREE_MAXV; x += 256) tpar[x] = -1;
@@ -149,7 +154,6 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
     // A: the best arc into every word whose node changed
     for (int i = 1 + wave; i < n; i += 4) {
       if (!dirty[i]) continue;
-      const int* __restrict__ row = S + (long)i * o;
       const int li = label[i];
       long long val[4], best = TREE_NONE;
 #pragma unroll
@@ -157,7 +161,7 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
         const int j = lane + 64 * k;
         val[k] = TREE_NONE;
         if (j < n) {
-          const int s = row[j];
+          const int s = score(i, j);
           if (s != TREE_FORBIDDEN && label[j] != li)
             val[k] = (long long)s - ((single_root && j == 0) ? TREE_ROOT_PENALTY : 0LL);
         }
@@ -198,10 +202,7 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
         in_u[x] = wsrc[bi];
       }
     }
-    if (__syncthreads_or(none)) {  // a node nothing may enter: no tree exists
-      if (tid == 0) status[g] = 2;
-      return;
-    }
+    if (__syncthreads_or(none)) return false;  // a node nothing may enter: no tree exists
     // C: follow the live nodes' arcs; node 0 (ROOT) is its own parent
     bool livex[2];
 #pragma unroll
@@ -262,10 +263,7 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
       if (lead[s]) newid[tid + 256 * s] = nid + before + inwave[s];
     }
     for (int q = 0; q < 8; ++q) total += wcnt[q];
-    if (nid + total > 2 * n) {  // (cannot happen: every cycle merges >= 2 of < n live nodes)
-      if (tid == 0) status[g] = 2;
-      return;
-    }
+    if (nid + total > 2 * n) return false;  // (cannot happen: every cycle merges >= 2 of < n live nodes)
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -292,10 +290,7 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
     if (word) dirty[tid] = moved && wsrc[tid] >= 0 && label[wsrc[tid]] == label[tid];
     __syncthreads();
   }
-  if (!done) {  // (cannot happen: n rounds contract n - 1 cycles at most)
-    if (tid == 0) status[g] = 2;
-    return;
-  }
+  if (!done) return false;  // (cannot happen: n rounds contract n - 1 cycles at most)
 
   // ---- expansion of the contraction forest, newest node first
   for (int x = tid; x < 2 * TREE_MAXV; x += 256) entered[x] = 0;
@@ -318,12 +313,42 @@ __global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ sco
     const bool word = tid > 0 && tid < n;
     const int hole = __syncthreads_or(word && (nh[tid] < 0 || nh[tid] >= n));
     const int roots = __syncthreads_count(word && nh[tid] == 0);
-    if (hole || (single_root && roots != 1)) {  // only trees with several ROOT children exist
-      if (tid == 0) status[g] = 2;
-      return;
-    }
-    if (word) pred[(base + tid) * 2] = nh[tid];
-    if (tid == 0) status[g] = 1;
+    if (hole || (single_root && roots != 1)) return false;  // only trees with several ROOT children exist
   }
-  tree_recount(gold, counts, pred, nh, n, v, base, g, tid);
+  return true;
+}
+
+// scores [b][v][o], n_nodes [b], pred [b][v][2] in/out, gold [b][v][2] and
+// counts [b][DECODE_COUNTS] both or neither, status [b].  grid = b, block = 256.
+__global__ void __launch_bounds__(256) k_tree_decode(const int* __restrict__ scores, int o,
+                                                     const int* __restrict__ n_nodes, int v, int single_root,
+                                                     int* __restrict__ pred, const int* __restrict__ gold,
+                                                     int* __restrict__ counts, int* __restrict__ status) {
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int n = tree_node_count(n_nodes[g], v, o);
+  const long base = (long)g * v;
+  const int* __restrict__ S = scores + base * o;
+  if (n < 2) {
+    if (tid == 0) status[g] = 0;
+    return;
+  }
+  const int K = tree_doublings(n);
+  __shared__ TreeSolve sh;
+
+  // ---- the fast path: pred's heads already are a tree
+  TreePred t = tree_pred_arc(pred, S, o, base, n, sh.jp, tid);
+  tree_pred_follow(t, n, K, sh.jp, tid);
+  if (t.is_tree && (!single_root || t.roots == 1)) {
+    if (tid == 0) status[g] = 0;
+    return;
+  }
+
+  const TreePlainScores score = {S, o};
+  if (!tree_solve(sh, score, n, K, single_root, tid)) {
+    if (tid == 0) status[g] = 2;
+    return;
+  }
+  if (tid > 0 && tid < n) pred[(base + tid) * 2] = sh.nh[tid];
+  if (tid == 0) status[g] = 1;
+  tree_recount(gold, counts, pred, sh.nh, n, v, base, g, tid);
 }

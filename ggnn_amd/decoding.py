@@ -1,9 +1,9 @@
 """Decoding: the chain decode -> marginals -> tree / projective pass ->
 confidences -> samples -> k-best, written once against a backend with the
-device binding's nine methods (``decode``, ``tree_decode``,
+device binding's ten methods (``decode``, ``tree_decode``,
 ``projective_decode``, ``projective_marginals``, ``tree_marginals``,
 ``arc_confidence``, ``tree_sample``, ``projective_sample``,
-``projective_kbest``):
+``projective_kbest``, ``tree_kbest``):
 heads.OutputHeads on the GPU, ``HostDecoder`` over evaluation.*_arrays for a
 model on a CPU device; and the model's decoding entries (``DecodingMixin``)."""
 from __future__ import annotations
@@ -29,12 +29,13 @@ _MBR_FAMILY = {"projective-mbr": "projective", "mbr": "nonprojective"}     # the
 SAMPLE_FAMILIES = ("nonprojective", "projective")                          # the distributions samples are drawn from
 
 
-def _sample_family(family):
-    """The ``sample_family`` / ``family`` keyword: "nonprojective" (all
-    dependency trees) or "projective"; anything else is a ValueError."""
+def _sample_family(family, keyword="sample_family"):
+    """The ``sample_family`` / ``kbest_family`` / ``family`` keyword:
+    "nonprojective" (all dependency trees) or "projective"; anything else is a
+    ValueError (``keyword`` opens its message)."""
     if isinstance(family, str) and family in SAMPLE_FAMILIES:
         return family
-    raise ValueError('sample_family must be "nonprojective" or "projective", got %r' % (family,))
+    raise ValueError('%s must be "nonprojective" or "projective", got %r' % (keyword, family))
 
 
 def _confidence_mode(confidence):
@@ -97,7 +98,7 @@ def _float32_marginals(host_form):
 
 
 class HostDecoder:
-    """OutputHeads' nine decoding methods over the host forms, numpy in and
+    """OutputHeads' ten decoding methods over the host forms, numpy in and
     out; the marginals as float32, without the host forms' span_max / cond /
     margin."""
     tree_decode = _in_place(_eval.tree_decode_arrays)
@@ -131,6 +132,11 @@ class HostDecoder:
         int32 [b]) of evaluation.projective_kbest_arrays."""
         return _eval.projective_kbest_arrays(scores, n_nodes, K, single_root)
 
+    def tree_kbest(self, scores, n_nodes, K, single_root=True):
+        """projective_kbest's four arrays of evaluation.tree_kbest_arrays (the
+        K best trees over all dependency trees)."""
+        return _eval.tree_kbest_arrays(scores, n_nodes, K, single_root)
+
 
 def _select(keep, x, fill):
     """x where keep, ``fill`` elsewhere: int32, in x's own array type."""
@@ -140,7 +146,7 @@ def _select(keep, x, fill):
 
 
 def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=True, confidence=False, samples=0,
-                 sample_seed=0, sample_family="nonprojective", kbest=0):
+                 sample_seed=0, sample_family="nonprojective", kbest=0, kbest_family="projective"):
     """The decode and what follows it, in launch order and in ``backend``'s
     array type (probs [b, v, o], probs_e [b, v, oe] float32, n_nodes int32
     [b], labels: the two heads' targets or None).  mode True / "projective":
@@ -163,8 +169,10 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     built for mode True / "projective", never an MBR mode's marginal scores --
     as kbest_heads [b, K, v], kbest_total [b, K], kbest_count [b] and
     kbest_status [b] (2 where a graph is not regular); kbest = 0 launches
-    nothing and adds nothing."""
-    sample_family = _sample_family(sample_family)
+    nothing and adds nothing.  kbest_family="nonprojective": the K best trees
+    over ALL dependency trees instead (backend.tree_kbest on the same scores
+    and counts; the same keys and fills)."""
+    sample_family, kbest_family = _sample_family(sample_family), _sample_family(kbest_family, "kbest_family")
     on_device, family, confidence = isinstance(probs, torch.Tensor), _MBR_FAMILY.get(mode), _confidence_mode(confidence)
     marginals = lambda kind: backend.projective_marginals if kind == "projective" else backend.tree_marginals
     head_scores = lambda: (tree_scores if on_device else _eval.tree_scores)(probs, n_nodes, probs.shape[1])
@@ -197,8 +205,8 @@ def decode_chain(backend, probs, probs_e, n_nodes, labels, mode, single_root=Tru
     if kbest:
         if family or not mode:       # (the chain's scores are the marginals', or there are none)
             scores = head_scores()
-        out["kbest_heads"], out["kbest_total"], out["kbest_count"], status = backend.projective_kbest(
-            scores, n_reg, kbest, single_root)
+        run = backend.projective_kbest if kbest_family == "projective" else backend.tree_kbest
+        out["kbest_heads"], out["kbest_total"], out["kbest_count"], status = run(scores, n_reg, kbest, single_root)
         out["kbest_status"] = _select(counts[:, 4] == 1, status, 2)
     return out
 
@@ -238,7 +246,7 @@ class DecodingMixin:
         return loss
 
     def _decode_forward(self, feed_dict, with_gold, tree=False, single_root=True, confidence=False, samples=0,
-                        sample_seed=0, sample_family="nonprojective", kbest=0):
+                        sample_seed=0, sample_family="nonprojective", kbest=0, kbest_family="projective"):
         """_eval_forward of a feed (default: the staged one), then decode_chain
         eagerly on the same stream (never inside a captured step).  Returns a
         dict: loss (scalar tensor), ph (the staged placeholders), b, v, n_nodes
@@ -267,7 +275,7 @@ class DecodingMixin:
             labels = [np.asarray(ph["target_values_head"], np.float32).reshape(b, v, o),
                       np.asarray(ph["target_values_edges"], np.float32).reshape(b, v, oe)] if with_gold else None
         r.update(decode_chain(backend, probs, probs_e, n, labels if with_gold else None, mode, single_root, confidence,
-                              samples, sample_seed, sample_family, kbest))
+                              samples, sample_seed, sample_family, kbest, kbest_family))
         return r
 
     def _host_pred(self, ph, b, v):
@@ -280,7 +288,7 @@ class DecodingMixin:
                                      np.asarray(ph["node_mask_edges"], np.float32).reshape(b, v, oe))
 
     def predict_batch(self, feed_dict=None, tree=False, single_root=True, confidence=False, samples=0, sample_seed=0,
-                      sample_family="nonprojective", kbest=0):
+                      sample_family="nonprojective", kbest=0, kbest_family="projective"):
         """The predicted tree of every graph of a batch: {'heads': [b, v],
         'labels': [b, v] (int32 numpy, zero-based columns of the two heads'
         arg-max as adj_mat_to_target(is_probability=True) picks them, -1 = no
@@ -347,13 +355,20 @@ class DecodingMixin:
         head probabilities AT THE RESOLUTION OF THE SCORES (every log2 p
         rounded to 2^-k bits and clamped below at -150; not normalised by any
         Z), -inf on the ranks >= count.  kbest = 0 launches nothing and adds
-        nothing; anything outside 0..KBEST_MAX is a ValueError."""
+        nothing; anything outside 0..KBEST_MAX is a ValueError.
+        kbest_family="nonprojective": the list is over ALL dependency trees
+        instead, crossing arcs included (ggnn_tree_kbest on the same scores:
+        the family of tree=True, whose total rank 0 has; 'kbest_count' =
+        min(K, number of trees), 'kbest_status' 2 = no tree exists, scores out
+        of range or not attempted); the keys, their shapes and fills and the
+        'kbest_log_prob' formula are the same.  Any other value is a
+        ValueError; without kbest the keyword launches nothing."""
         tree = _tree_mode(tree, confidence, "predict_batch")
-        sample_family = _sample_family(sample_family)
+        sample_family, kbest_family = _sample_family(sample_family), _sample_family(kbest_family, "kbest_family")
         samples = _eval._count_in_range("samples", samples, _eval.SAMPLE_MAX, 0)
         kbest = _eval._count_in_range("kbest", kbest, _eval.KBEST_MAX, 0)
         r = self._decode_forward(feed_dict, False, tree, single_root, confidence, samples, sample_seed, sample_family,
-                                 kbest)
+                                 kbest, kbest_family)
         ph, b, v, pred = r["ph"], r["b"], r["v"], r["pred"]
         if pred is None:
             pred = self._host_pred(ph, b, v)
@@ -394,18 +409,23 @@ class DecodingMixin:
         for i, feed in enumerate(self.make_minibatch_iterator(self.process_raw_graphs(raw, False), False)):
             yield i, self.predict_batch(feed, *args, sample_seed=(int(seed) + i) % 2 ** 64, **kwargs)
 
-    def parse_kbest(self, raw_data, k, single_root=True):
+    def parse_kbest(self, raw_data, k, single_root=True, family="projective"):
         """The k best projective dependency trees of raw btb sentences
-        (parse's input), best first (predict_batch(kbest=k)).  Returns (trees,
+        (parse's input), best first (predict_batch(kbest=k)); with
+        family="nonprojective" the k best over ALL dependency trees
+        (predict_batch(kbest=k, kbest_family="nonprojective"): the first entry
+        is parse(tree=True)'s tree where the scores have one best tree).
+        Returns (trees,
         log_probs): trees[s] a list of up to k entries in the JSON's 'targets'
         form [[head, label], ...] for nodes 1..n-1 (the label one-based: the
         label head's arg-max, which does not depend on the head), log_probs[s]
         each one's 'kbest_log_prob', aligned and non-increasing.  A sentence
         with fewer than k projective trees yields those it has; a sentence
         process_raw_graphs drops yields []."""
+        family = _sample_family(family, "family")
         raw_data = list(raw_data)
         out, log_probs = [[] for _ in raw_data], [[] for _ in raw_data]
-        for _, p in self._predict_raw(raw_data, False, single_root, kbest=k):
+        for _, p in self._predict_raw(raw_data, False, single_root, kbest=k, kbest_family=family):
             for g, s in enumerate(p["sentences_id"]):
                 for r in range(int(p["kbest_count"][g])):
                     out[s].append(_targets_rows(p["kbest_heads"][g, r], p["labels"][g], int(p["n_nodes"][g])))

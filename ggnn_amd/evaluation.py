@@ -831,6 +831,91 @@ def projective_kbest_arrays(scores, n_nodes, K, single_root=True):
     return heads, totals, count, status
 
 
+# ------------------------------------- k-best trees over all dependency trees
+# Host form of ``ggnn_tree_kbest`` (include/ggnn.h, csrc/k_tree_kbest.h):
+# Lawler's partitioning over _max_arborescence.  A subproblem = a partial head
+# assignment fix[w] (-1 = free) and a list of excluded arcs (word, head); its
+# best tree is the maximum arborescence of the masked scores.  The tree h that
+# becomes rank r leaves one child per free word w, in increasing w: the free
+# words below w fixed to h, (w, h[w]) excluded on top of the inherited
+# exclusions.  The pool holds every solved child; the next rank is its first
+# entry by (larger total, smaller parent rank, smaller word).
+def _masked_scores(s, n, fix, excluded):
+    """int32 [n, n]: s with the row of every fixed word forbidden except at
+    its head and every excluded arc forbidden."""
+    m = np.array(np.asarray(s)[:n, :n], np.int32)
+    for w in range(1, n):
+        if fix[w] >= 0:
+            keep = m[w, fix[w]]
+            m[w, :] = TREE_FORBIDDEN
+            m[w, fix[w]] = keep
+    for w, h in excluded:
+        m[w, h] = TREE_FORBIDDEN
+    return m
+
+
+def _tree_kbest_graph(s, n, single_root, K):
+    """[(total, heads)] of one graph: up to K trees, best first."""
+    heads, _ = _max_arborescence(s, n, single_root)
+    if heads is None:
+        return []
+    ranks, pool = [], {}                        # pool: (parent rank, word) -> (total, heads, fix, excluded)
+    cand = (tree_total(s, heads, n), heads, [-1] * n, [])
+    while True:
+        total, h, fix, excluded = cand
+        r = len(ranks)
+        ranks.append((total, h))
+        if r + 1 == K:
+            break
+        fix = list(fix)
+        for w in range(1, n):
+            if fix[w] >= 0:
+                continue
+            ex = excluded + [(w, h[w])]
+            child, _ = _max_arborescence(_masked_scores(s, n, fix, ex), n, single_root)
+            if child is not None:
+                pool[(r, w)] = (tree_total(s, child, n), child, list(fix), ex)
+            fix[w] = h[w]
+        if not pool:
+            break
+        first = min(pool, key=lambda pw: (-pool[pw][0], pw[0], pw[1]))
+        cand = pool.pop(first)
+    return ranks
+
+
+def tree_kbest_arrays(scores, n_nodes, K, single_root=True):
+    """The host form of ``ggnn_tree_kbest`` (include/ggnn.h): the K best trees
+    over ALL dependency trees (arcs may cross) of every graph in order.
+    scores int32 [b, v, o] (``tree_scores``), n_nodes [b], 1 <= K <=
+    KBEST_MAX.  Returns (heads int32 [b, K, v]: the head of word i in the tree
+    of rank k, -1 on node 0, rows >= n and ranks >= count; totals int32
+    [b, K]: the tree's sum of scores, TREE_FORBIDDEN on ranks >= count; count
+    int32 [b]; status int32 [b]: 0 = n < 2, 1 = count >= 1, 2 = S * (n - 1) >=
+    2^30 for the largest absolute allowed score S, or no tree exists).  Rank 0
+    is _max_arborescence's tree, ties included; the list for K is a prefix of
+    the list for a larger K."""
+    s, b, v, o, nn = _head_input(scores, n_nodes, "scores", np.int32, "tree k-best needs")
+    K = _count_in_range("K", K, KBEST_MAX)
+    heads = np.full((b, K, v), -1, np.int32)
+    totals = np.full((b, K), TREE_FORBIDDEN, np.int32)
+    count, status = np.zeros(b, np.int32), np.zeros(b, np.int32)
+    for g in range(b):
+        n = int(nn[g])
+        if n < 2:
+            continue
+        status[g] = 2
+        if not _range_ok(s[g], n):
+            continue
+        ranks = _tree_kbest_graph(s[g], n, bool(single_root), K)
+        if not ranks:
+            continue
+        status[g], count[g] = 1, len(ranks)
+        for r, (total, h) in enumerate(ranks):
+            totals[g, r] = total
+            heads[g, r, 1:n] = h[1:]
+    return heads, totals, count, status
+
+
 # ------------------------------------------------- projective arc marginals
 # Host form of ``ggnn_projective_marginals`` (include/ggnn.h, csrc/k_marg.h):
 # the sum-product twin of _eisner (inside pass, explicit outside pass), in log

@@ -510,8 +510,25 @@ class OutputHeads:
         the scores are out of range).  workspace: a uint8 tensor to use instead
         of the binding's own (grown on demand; needed for v >
         ggnn_projective_kbest_lds_maxn(K) only)."""
+        return self._kbest_pass("projective_kbest", scores, n_nodes, K, single_root, workspace)
+
+    def tree_kbest(self, scores, n_nodes, K, single_root=True, workspace=None):
+        """The K best trees over ALL dependency trees (arcs may cross) of every
+        graph, best first, on the current stream (ggnn_tree_kbest: Lawler's
+        partitioning over ``tree_decode``'s solver, 2 K - 1 launches; rank 0 is
+        ``tree_decode``'s tree).  Arguments, checks and the returned (heads,
+        totals, count, status) are ``projective_kbest``'s; count =
+        min(K, number of trees), status 2 = no tree exists or the scores are
+        out of range.  workspace: a uint8 tensor to use instead of the
+        binding's own (grown on demand, kept per pass:
+        ggnn_tree_kbest_workspace_bytes(b, v, K) bytes)."""
+        return self._kbest_pass("tree_kbest", scores, n_nodes, K, single_root, workspace)
+
+    def _kbest_pass(self, name, scores, n_nodes, K, single_root, workspace):
+        """projective_kbest / tree_kbest: ggnn_<name> with its outputs and its
+        workspace."""
         K = _count_in_range("K", K, _lib.KBEST_MAX)
-        b, v, o, dev, run = self._pass("projective_kbest", scores, "scores", torch.int32, n_nodes, workspace, K)
+        b, v, o, dev, run = self._pass(name, scores, "scores", torch.int32, n_nodes, workspace, K)
         heads = torch.empty(b, K, v, dtype=torch.int32, device=dev)
         totals = torch.empty(b, K, dtype=torch.int32, device=dev)
         count = torch.empty(b, dtype=torch.int32, device=dev)

@@ -861,6 +861,57 @@ int ggnn_projective_kbest(const ggnn_dims* d,           /* b, v used */
                           int32_t* status,              /* device [b] out */
                           void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* The K best trees over ALL dependency trees (arcs may cross) of every graph,
+ * in order: ggnn_projective_kbest's twin in the family of ggnn_tree_decode.
+ * Arguments, argument order, limits, the range rule and the outputs' fills are
+ * ggnn_projective_kbest's: heads[g][k][i] the head of word i in the tree of
+ * rank k, -1 on node 0, rows >= n and ranks >= count[g]; totals[g][k] = sum_i
+ * scores[i][head_i], GGNN_TREE_FORBIDDEN on ranks >= count[g]; count[g] in
+ * 0..K = min(K, number of trees); status[g] = 0 n < 2 (count 0), 1 count >= 1,
+ * 2 the range rule is violated or no tree exists (count 0).  single_root: every
+ * tree has one ROOT child.
+ * Lawler's partitioning over ggnn_tree_decode's Chu-Liu/Edmonds solver.  A
+ * subproblem = a partial head assignment and a list of excluded arcs; its best
+ * tree is the maximum arborescence of the scores with a fixed word's row
+ * forbidden except at its head and every excluded arc forbidden.  Rank 0 is
+ * the unconstrained optimum: ggnn_tree_decode's tree when that pass runs, ties
+ * included.  The tree h that becomes rank r leaves one child per word w its
+ * subproblem leaves free, in increasing w: the free words below w fixed to
+ * their heads in h, (w, h[w]) excluded on top of the inherited exclusions (at
+ * most K - 1 on a chain).  Every solved child's total goes to a pool; rank r +
+ * 1 is the pool's first entry by: larger total, then smaller parent rank, then
+ * smaller word.  The children partition their parent's subproblem without h,
+ * so the list holds distinct trees; nothing depends on K, so the list for K is
+ * a prefix of the list for any larger K.
+ * 2 K - 1 stream-ordered launches, no host synchronisation: take(0), then
+ * solve(r - 1) (grid b * (v - 1): child (r - 1, w) of graph g, one workgroup
+ * each; those of absent ranks, of rows >= n and of fixed words leave at once)
+ * and take(r) (grid b: the pool's first entry, its child solved again for the
+ * heads, which are never stored) for r = 1 .. K - 1; K = 1 launches take(0)
+ * alone.  At most (K - 1)(n - 1) + K contractions per graph.
+ * Storage: ggnn_tree_kbest_workspace_bytes(b, v, K) = b * 4 * (K * (2 v + 16)
+ * + 16) bytes (0 for b < 1, v < 1 or K outside 1..GGNN_KBEST_MAX): per graph 16
+ * int32 (the ranks so far), the pool K * v and per rank v + 16 (fix[v], 15
+ * exclusions, their number); nothing of size v^2.  A smaller workspace is
+ * rejected before any launch.  Needs v <= o, v <= GGNN_TREE_MAXV, o <= 1024, 1
+ * <= K <= GGNN_KBEST_MAX, b * (v - 1) < 2^31.  Workgroups of 256 threads, 30.2
+ * KiB of LDS each.  No atomics, nothing between the workgroups of a launch,
+ * every loop bounded by a function of n and K, every tie by index order.
+ * Allocation-free, legal under stream capture, bit-reproducible; booked under
+ * the heads kernel kind. */
+size_t ggnn_tree_kbest_workspace_bytes(int32_t b, int32_t v, int32_t K);
+int ggnn_tree_kbest(const ggnn_dims* d,                 /* b, v used */
+                    const int32_t* scores,              /* device [b][v][o] */
+                    int32_t o,
+                    const int32_t* n_nodes,             /* device [b] */
+                    int32_t single_root,                /* 0 / 1 */
+                    int32_t K,
+                    int32_t* heads,                     /* device [b][K][v] out */
+                    int32_t* totals,                    /* device [b][K] out */
+                    int32_t* count,                     /* device [b] out */
+                    int32_t* status,                    /* device [b] out */
+                    void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+
 /* Optional per-kernel timing (HIP events around every launch of the library
  * on the launch's stream), used by bench.py for the roofline.  Not for use
  * under graph capture.  total_ms / launches: arrays of GGNN_NUM_KERNEL_KINDS. */
