@@ -37,6 +37,7 @@ EXPORTED = (
     "ggnn_projective_marginals_workspace_bytes", "ggnn_projective_marginals", "ggnn_arc_confidence",
     "ggnn_tree_marginals_workspace_bytes", "ggnn_tree_marginals",
     "ggnn_tree_loss_workspace_bytes", "ggnn_tree_loss", "ggnn_tree_loss_dev",
+    "ggnn_margin_loss_workspace_bytes", "ggnn_margin_loss", "ggnn_margin_loss_dev",
     "ggnn_tree_sample_workspace_bytes", "ggnn_tree_sample",
     "ggnn_projective_sample_workspace_bytes", "ggnn_projective_sample",
     "ggnn_projective_kbest_lds_maxn", "ggnn_projective_kbest_workspace_bytes", "ggnn_projective_kbest",
@@ -165,6 +166,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
         lib.ggnn_tree_loss.argtypes = [_DP, _P, I32, _P, _P, I32, I32, F] + [_P] * 6 + [ctypes.c_size_t, _P]
         lib.ggnn_tree_loss_dev.restype = _I
         lib.ggnn_tree_loss_dev.argtypes = [_DP, _P, I32, _P, _P, I32, I32, _P] + [_P] * 6 + [ctypes.c_size_t, _P]
+        lib.ggnn_margin_loss_workspace_bytes.restype = ctypes.c_size_t
+        lib.ggnn_margin_loss_workspace_bytes.argtypes = [I32, I32, I32, I32]
+        lib.ggnn_margin_loss.restype = _I
+        lib.ggnn_margin_loss.argtypes = [_DP, _P, I32, _P, _P, I32, I32, F, F] + [_P] * 8 + [ctypes.c_size_t, _P]
+        lib.ggnn_margin_loss_dev.restype = _I
+        lib.ggnn_margin_loss_dev.argtypes = [_DP, _P, I32, _P, _P, I32, I32, F, _P] + [_P] * 8 + [ctypes.c_size_t, _P]
         lib.ggnn_projective_kbest_lds_maxn.restype = I32
         lib.ggnn_projective_kbest_lds_maxn.argtypes = [I32]
         lib.ggnn_arc_confidence.restype = _I

@@ -26,6 +26,7 @@
 #include "k_marg.h"
 #include "k_lapl.h"
 #include "k_tree_loss.h"
+#include "k_margin_loss.h"
 #include "k_gemm.h"
 #include "k_gemm_ring.h"
 #include "k_generic.h"
@@ -1911,6 +1912,100 @@ int ggnn_tree_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, c
   if (!target_num) return fail(GGNN_EINVAL, "tree_loss_dev: NULL target_num");
   return tree_loss_impl(d, probs_head, o, gold_head, n_nodes, family, single_root, 0.f, target_num, marg, logz, status,
                         used, loss_inout, workspace, workspace_bytes, stream);
+}
+
+// the max-margin training loss (k_margin_loss.h around the family's decoder);
+// booked under the heads kind.  The workspace, every part rounded up to 256
+// bytes: n_eff int32 [b], term double [b], the gold heads int32 [b][v], pred
+// int32 [b][v][2], s' int32 [b][v][o], then the decoder's own.
+struct MarginLayout {
+  size_t term, goldh, pred, scores, inner, total;
+};
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static MarginLayout margin_layout(int32_t b, int32_t v, int32_t o, int32_t family) {
+  MarginLayout L;
+  L.term = up256((size_t)b * 4);
+  L.goldh = L.term + up256((size_t)b * 8);
+  L.pred = L.goldh + up256((size_t)b * v * 4);
+  L.scores = L.pred + up256((size_t)b * v * 8);
+  L.inner = L.scores + up256((size_t)b * v * (size_t)o * 4);
+  L.total = L.inner + (family == 1 ? ggnn_projective_decode_workspace_bytes(b, v) : ggnn_tree_decode_workspace_bytes(b, v));
+  return L;
+}
+// k of evaluation.tree_score_shift: the largest k <= 16 with 150 * 2^k * v * (v + 1) <= 2^30
+static int tree_score_shift(int32_t v) {
+  int k = 16;
+  while (k > 0 && (150LL * v * ((long long)v + 1) << k) > (1LL << 30)) --k;
+  return k;
+}
+size_t ggnn_margin_loss_workspace_bytes(int32_t b, int32_t v, int32_t o, int32_t family) {
+  if (b < 1 || v < 1 || o < 1) return 0;
+  return margin_layout(b, v, o, family).total;
+}
+static int margin_loss_impl(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                            const int32_t* n_nodes, int32_t family, int32_t single_root, float cost, float target_num,
+                            const float* tn_dev, float* marg, int32_t* heads, float* value, int32_t* hamming,
+                            int32_t* status, int32_t* used, float* loss_inout, void* workspace, size_t workspace_bytes,
+                            ggnn_stream_t stream) {
+  const char* const name = "margin_loss";
+  const bool null_arg = !probs_head || !gold_head || !n_nodes || !marg || !heads || !value || !hamming || !status ||
+                        !used || !loss_inout || !workspace;
+  if (int rc = decode_args(name, d, o, nullptr, true, single_root, null_arg)) return rc;
+  if (family != 0 && family != 1)
+    return fail(GGNN_EINVAL, "margin_loss: family must be 0 (all trees) or 1 (projective)");
+  if (!(cost >= 0.f && cost <= 64.f)) return fail(GGNN_EINVAL, "margin_loss: cost must lie in 0..64");  // (a NaN fails)
+  if (!tn_dev && !(target_num > 0.f)) return fail(GGNN_EINVAL, "margin_loss: target_num must be > 0");
+  if (int rc = no_alias(name, marg, probs_head)) return rc;
+  const MarginLayout L = margin_layout(d->b, d->v, o, family);
+  if (int rc = decode_workspace(name, L.total, workspace, workspace_bytes)) return rc;
+  char* const ws = (char*)workspace;
+  int* n_eff = (int*)ws;
+  double* term = (double*)(ws + L.term);
+  int* goldh = (int*)(ws + L.goldh);
+  int* pred = (int*)(ws + L.pred);
+  int* scores = (int*)(ws + L.scores);
+  const int k = tree_score_shift(d->v);
+  const double scale = (double)(1 << k);
+  const int C = (int)std::rint((double)cost * scale / M_LN2);
+  if (int rc = heads_launch(stream, [&](hipStream_t s) {
+#define MLS(NI_)                                                                                                   \
+  hipLaunchKernelGGL(k_tree_loss_gold<NI_>, dim3((unsigned)d->b), dim3(256), 0, s, gold_head, probs_head, (int)o, \
+                     (const int*)n_nodes, (int)d->v, (int)family, (int)single_root, n_eff);                       \
+  hipLaunchKernelGGL(k_margin_scores<NI_>, dim3((unsigned)d->b), dim3(256), 0, s, gold_head, probs_head, (int)o,  \
+                     (const int*)n_eff, (int)d->v, scale, -150.0 * scale, C, scores, goldh, pred)
+        if (o <= 256) { MLS(4); }
+        else { MLS(HEAD_MAXO / 64); }
+#undef MLS
+      }))
+    return rc;
+  // the family's best tree of s' over the eligible graphs (n_eff = 0: status 0, nothing read or written)
+  void* inner = L.total > L.inner ? (void*)(ws + L.inner) : nullptr;
+  if (int rc = (family == 1 ? ggnn_projective_decode : ggnn_tree_decode)(
+          d, scores, o, n_eff, single_root, pred, nullptr, nullptr, status, inner, L.total - L.inner, stream))
+    return rc;
+  return heads_launch(stream, [&](hipStream_t s) {
+    hipLaunchKernelGGL(k_margin_fold, dim3((unsigned)d->b), dim3(256), 0, s, probs_head, gold_head, (int)o,
+                       (const int*)n_eff, (int)d->v, (const int*)goldh, (const int*)pred, (const int*)status,
+                       (double)cost, marg, (int*)heads, value, (int*)hamming, (int*)used, term);
+    hipLaunchKernelGGL(k_margin_sum, dim3(1), dim3(64), 0, s, (const int*)used, (const double*)term, (int)d->b,
+                       target_num, tn_dev, loss_inout);
+  });
+}
+int ggnn_margin_loss(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                     const int32_t* n_nodes, int32_t family, int32_t single_root, float cost, float target_num,
+                     float* marg, int32_t* heads, float* value, int32_t* hamming, int32_t* status, int32_t* used,
+                     float* loss_inout, void* workspace, size_t workspace_bytes, ggnn_stream_t stream) {
+  return margin_loss_impl(d, probs_head, o, gold_head, n_nodes, family, single_root, cost, target_num, nullptr, marg,
+                          heads, value, hamming, status, used, loss_inout, workspace, workspace_bytes, stream);
+}
+int ggnn_margin_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                         const int32_t* n_nodes, int32_t family, int32_t single_root, float cost,
+                         const float* target_num, float* marg, int32_t* heads, float* value, int32_t* hamming,
+                         int32_t* status, int32_t* used, float* loss_inout, void* workspace, size_t workspace_bytes,
+                         ggnn_stream_t stream) {
+  if (!target_num) return fail(GGNN_EINVAL, "margin_loss_dev: NULL target_num");
+  return margin_loss_impl(d, probs_head, o, gold_head, n_nodes, family, single_root, cost, 0.f, target_num, marg, heads,
+                          value, hamming, status, used, loss_inout, workspace, workspace_bytes, stream);
 }
 
 // dependency trees drawn from the distribution of ggnn_tree_marginals

@@ -1308,6 +1308,104 @@ def tree_loss_arrays(probs_head, gold_head, n_nodes, family, single_root, target
     return term, marg, logz, status, used
 
 
+# ------------------------------------------------------- the max-margin loss
+# Host form of ``ggnn_margin_loss`` (include/ggnn.h, csrc/k_margin_loss.h): the
+# structured hinge loss over cost-augmented decoding (Taskar et al. 2004; the
+# objective of MSTParser and of Kiperwasser & Goldberg 2016).  Per graph, with
+# p the softmax of the head logits z, y the gold heads and c the margin cost,
+#   T* = the best tree of the family under ln p[d][h] + c [h != y_d],
+#   l  = sum over the words d with T*_d != y_d of ln p[d][T*_d] - ln p[d][y_d] + c,
+#   L  = max(0, l),    dL/dz[d][k] = onehot(T*)[d][k] - y[d][k] where l > 0, else 0
+# (every tree has one head per word, so the rows' logsumexp cancels between two
+# trees: decoding ln p is decoding the logits, and no softmax term is left in
+# the gradient).  T* is found on the integers of tree_scores, so it is the
+# maximiser up to their resolution: l may fall short of the true maximum by at
+# most 1.5 (n - 1) ln 2 * 2^-k.
+MARGIN_LOSS_KINDS = {"nonprojective-margin": 0, "projective-margin": 1}
+MARGIN_COST_MAX = 64.0         # keeps |s'| <= 150 * 2^k: the decoders' range rule holds as for tree_scores
+
+
+def margin_cost(cost):
+    """``cost`` as the float32 the library takes, checked: finite, 0 <= cost <= 64."""
+    try:
+        c = float("nan") if isinstance(cost, (bool, str)) or cost is None else float(np.float32(cost))
+    except (TypeError, ValueError):
+        c = float("nan")
+    if not (np.isfinite(c) and 0.0 <= c <= MARGIN_COST_MAX):
+        raise ValueError("the margin cost must be a number in 0..%g, got %r" % (MARGIN_COST_MAX, cost))
+    return c
+
+
+def margin_cost_units(cost, v):
+    """C of the cost-augmented scores: rint(cost * 2^k / ln 2), k = tree_score_shift(v)."""
+    return int(np.rint(margin_cost(cost) * float(2 ** tree_score_shift(v)) / np.log(2.0)))
+
+
+def margin_scores(scores, gold_heads, cost, v):
+    """s' of one batch: scores int32 [b, v, o] (tree_scores') with C added on
+    every allowed arc (d, j) with j != gold_heads[g][d].  gold_heads int [b, v]."""
+    s = np.asarray(scores, np.int32)
+    y = np.asarray(gold_heads).astype(np.int64)
+    j = np.arange(s.shape[2]).reshape(1, 1, -1)
+    add = (s != TREE_FORBIDDEN) & (j != y[:, :, None])
+    return np.where(add, s.astype(np.int64) + margin_cost_units(cost, v), s).astype(np.int32)
+
+
+def margin_loss_arrays(probs_head, gold_head, n_nodes, family, single_root, target_num, cost):
+    """The host form of ``ggnn_margin_loss``: returns (loss_term, marg float32
+    [b, v, o], heads int32 [b, v], value float32 [b], hamming int32 [b], status
+    int32 [b], used int32 [b]).  A graph that gold_tree_ok admits is decoded on
+    its cost-augmented scores (_max_arborescence / _eisner, always solved);
+    status is the decoder's (1 solved, 2 none; 0 for a graph that is not
+    admitted), used = admitted and status 1.  For a used graph heads holds T*
+    on the words 1..n-1 (-1 elsewhere and on every other graph), hamming the
+    words with T*_d != y_d, value max(0, l), and marg onehot(T*) where l > 0, a
+    copy of gold_head otherwise; any other graph's marg is a copy of
+    probs_head.  loss_term = (sum over the used graphs of max(0, l) + sum_d ln
+    p[d][y_d]) / target_num: what the call adds to head 0's loss, the second
+    part cancelling the cross-entropy the heads' forward has put there."""
+    family = _tree_loss_family(family)
+    c = margin_cost(cost)
+    p = np.asarray(probs_head, np.float32)
+    y = np.asarray(gold_head, np.float32)
+    b, v, o = p.shape
+    ok = gold_tree_ok(y, p, n_nodes, family, single_root)
+    nn = _node_counts(n_nodes, b, v, o)
+    gold = np.where((y == 1).any(axis=2), (y == 1).argmax(axis=2), -1)
+    s2 = margin_scores(tree_scores(p, nn, v), gold, c, v)
+    marg = p.copy()
+    heads = np.full((b, v), -1, np.int32)
+    value = np.zeros(b, np.float32)
+    hamming, status, used = np.zeros(b, np.int32), np.zeros(b, np.int32), np.zeros(b, np.int32)
+    total = 0.0
+    for g in range(b):
+        if not ok[g]:
+            continue
+        n = int(nn[g])
+        if family == 1:
+            t = _eisner(s2[g], n, bool(single_root)) if _range_ok(s2[g], n) else None
+        else:
+            t = _max_arborescence(s2[g], n, bool(single_root))[0]
+        if t is None:
+            status[g] = 2
+            continue
+        status[g] = used[g] = 1
+        w = np.arange(1, n)
+        t, yg = np.asarray(t[1:n], np.int64), gold[g, 1:n]
+        heads[g, 1:n] = t
+        lp = np.log(p[g].astype(np.float64), where=p[g] > 0, out=np.zeros((v, o)))
+        wrong = t != yg
+        loss = float((lp[w, t] - lp[w, yg] + c)[wrong].sum())
+        hamming[g] = int(wrong.sum())
+        value[g] = max(0.0, loss)
+        marg[g] = y[g]
+        if loss > 0:
+            marg[g] = 0
+            marg[g, w, t] = 1
+        total += max(0.0, loss) + float(lp[w, yg].sum())
+    return total / float(target_num), marg, heads, value, hamming, status, used
+
+
 # ------------------------------------------------ sampling dependency trees
 # Host form of ``ggnn_tree_sample`` (include/ggnn.h, csrc/k_tree_sample.h):
 # trees drawn from the distribution over ALL dependency trees whose arc

@@ -11,7 +11,7 @@ shapes never pay for a capture); its second batch is captured and replayed.
 What stays fixed across replays of one graph (its key: batch shape (b, v),
 the word_inputs width, the dropout keep probabilities, train / eval, the task,
 whether Adam is in the graph and then grad_scale, the word table's layout,
-params['structured_loss'] with its root mode, and the host scalars below): every device pointer (the step owns its engine --
+params['structured_loss'] with its root mode (and, for the margin kinds, the cost), and the host scalars below): every device pointer (the step owns its engine --
 adjacency, workspaces -- and its heads workspace; the variables, their Adam
 slots and the flat gradient buffer belong to the model), every launch shape
 and every host scalar the library bakes into a launch.  Of those scalars the

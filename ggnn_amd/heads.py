@@ -7,7 +7,9 @@
   (chem_tensorflow_dense.py:439-516) with ``MLP(2h, o, [], keep)``
   (utils.py:40-84) and the btb cross-entropy (chem_tensorflow.py:349-403);
   not in the reference: ``tree_loss=`` turns head 0's loss into the negative
-  log-likelihood of the gold tree (``ggnn_tree_loss``, ``csrc/k_tree_loss.h``).
+  log-likelihood of the gold tree (``ggnn_tree_loss``, ``csrc/k_tree_loss.h``)
+  or, with a cost, into the structured hinge over cost-augmented decoding
+  (``ggnn_margin_loss``, ``csrc/k_margin_loss.h``).
 
 Both run in libggnn.so (``ggnn_embed_*``, ``ggnn_heads_*``; kernels in
 ``csrc/k_head.h``); torch tensors only hold device memory.  The autograd
@@ -184,6 +186,10 @@ class OutputHeads:
         # stand in head 0's probs place in the backward, and used int32 [b];
         # None after a forward without it
         self.tree_marg = self.tree_used = None
+        # the last forward's max-margin loss (tree_loss= with a cost): T* int32
+        # [b, v], max(0, l) float32 [b] and the Hamming distance int32 [b]; None
+        # after a forward without it
+        self.margin_heads = self.margin_value = self.margin_hamming = None
 
     def _table(self, heads, labels, probs, dws=None, dbs=None):
         arr = (OutputHead * len(heads))()
@@ -206,6 +212,10 @@ class OutputHeads:
         on the same stream: ln Z / target_num is added into loss[0]); the
         marginals and used [b] stay on the object (tree_marg, tree_used) and
         the next ``backward`` takes the marginals in head 0's probs place.
+        With a fourth element, the margin cost, the max-margin loss runs in
+        its place (``margin_loss`` below): tree_marg then holds onehot(T*), the
+        gold block or the probabilities, and margin_heads, margin_value and
+        margin_hamming stay on the object as well.
         The returned probs are the softmax either way."""
         if tree_loss is not None and labels is None:
             raise ValueError("tree_loss needs labels")
@@ -236,7 +246,12 @@ class OutputHeads:
                        "ggnn_heads_forward")
         self._saved = (b, v, h)
         self.tree_marg = self.tree_used = None
-        if tree_loss is not None:
+        self.margin_heads = self.margin_value = self.margin_hamming = None
+        if tree_loss is not None and len(tree_loss) == 4:
+            family, single_root, n_nodes, cost = tree_loss
+            out = self.margin_loss(probs[0], labels[0], n_nodes, family, single_root, target_num, loss, cost)
+            self.tree_marg, self.margin_heads, self.margin_value, self.margin_hamming, _, self.tree_used = out
+        elif tree_loss is not None:
             family, single_root, n_nodes = tree_loss
             self.tree_marg, _, _, self.tree_used = self.tree_loss(probs[0], labels[0], n_nodes, family, single_root,
                                                                   target_num, loss)
@@ -272,6 +287,43 @@ class OutputHeads:
             _ptr(target_num) if on_dev else float(target_num), _ptr(marg), _ptr(logz), _ptr(status), _ptr(used),
             _ptr(loss), entry="tree_loss_dev" if on_dev else "tree_loss")
         return marg, logz, status, used
+
+    def margin_loss(self, probs_head, gold_head, n_nodes, family, single_root, target_num, loss, cost=1.0,
+                    workspace=None):
+        """The max-margin loss on the current stream (ggnn_margin_loss,
+        include/ggnn.h): the structured hinge over cost-augmented decoding.
+        Arguments and checks are ``tree_loss``'s; cost: the margin per wrong
+        head, 0..64.  ``loss[0] += (sum over the used graphs of max(0, l) +
+        sum_d ln p[d][y_d]) / target_num``: the hinge in the place of the
+        cross-entropy the heads' forward has put there.  Returns (marg float32
+        [b, v, o], heads int32 [b, v], value float32 [b], hamming int32 [b],
+        status int32 [b], used int32 [b]): a used graph's marg holds
+        onehot(T*) where its loss is positive and its gold block otherwise
+        (what the heads' backward takes in the probabilities' place), any
+        other graph's a copy of probs_head; heads is T* (-1 on node 0, the
+        padding and the graphs that are not used)."""
+        family = {"nonprojective": 0, "projective": 1}.get(family, family)
+        if family not in (0, 1):
+            raise ValueError("family must be 0 / 'nonprojective' or 1 / 'projective'")
+        if isinstance(cost, (bool, str)) or cost is None or not 0.0 <= float(cost) <= 64.0:
+            raise ValueError("cost must be a number in 0..64, got %r" % (cost,))
+        _check_tensor(probs_head, "probs_head", torch.float32)
+        b, v, o, dev, run = self._pass("margin_loss", probs_head, "probs_head", torch.float32, n_nodes, workspace,
+                                       probs_head.shape[2], family)
+        _check_tensor(gold_head, "gold_head", torch.float32)
+        if gold_head.shape != probs_head.shape or gold_head.device != dev:
+            raise ValueError("gold_head must have probs_head's shape and device")
+        if loss.dtype != torch.float32 or loss.device != dev or loss.numel() < 1 or not loss.is_contiguous():
+            raise ValueError("loss must be a contiguous float32 tensor on %s" % dev)
+        marg = torch.empty_like(probs_head)
+        heads = torch.empty(b, v, dtype=torch.int32, device=dev)
+        value = torch.empty(b, dtype=torch.float32, device=dev)
+        hamming, status, used = (torch.empty(b, dtype=torch.int32, device=dev) for _ in range(3))
+        on_dev = isinstance(target_num, torch.Tensor)
+        run(_ptr(gold_head), _ptr(n_nodes), int(family), int(bool(single_root)), float(cost),
+            _ptr(target_num) if on_dev else float(target_num), _ptr(marg), _ptr(heads), _ptr(value), _ptr(hamming),
+            _ptr(status), _ptr(used), _ptr(loss), entry="margin_loss_dev" if on_dev else "margin_loss")
+        return marg, heads, value, hamming, status, used
 
     def backward(self, hT, h0, heads, labels, probs, target_num=1.0, d_loss=None, dws=None, dbs=None, dhT=None,
                  dh0=None):

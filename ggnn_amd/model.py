@@ -32,7 +32,12 @@ chem_tensorflow.py:70-136) that the hot path reads, with the same names:
 * not in the reference: ``params['structured_loss']`` ("nonprojective" /
   "projective"): the head's loss as the negative log-likelihood of the gold
   tree (``ggnn_tree_loss`` after the heads' forward, in every step body;
-  ``ops['tree_loss_used']``: the graphs of the last step it applied to)
+  ``ops['tree_loss_used']``: the graphs of the last step it applied to);
+  "nonprojective-margin" / "projective-margin": the structured hinge loss over
+  cost-augmented decoding in its place (``ggnn_margin_loss``), with
+  ``params['structured_loss_margin']`` (default 1.0) the cost of a wrong head
+  (``ops['margin_loss_hamming']``: the wrong heads of the last step's
+  cost-augmented trees, per graph)
 
 The arithmetic runs in libggnn.so; torch tensors only hold device memory and
 carry the autograd graph around the call.
@@ -151,9 +156,15 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         self.params = self.default_params()
         if params:
             self.params.update(params)
-        if self.params.get("structured_loss") not in (None,) + tuple(_eval.TREE_LOSS_FAMILIES):
-            raise ValueError("params['structured_loss'] must be None, 'nonprojective' or 'projective', got %r"
-                             % (self.params["structured_loss"],))
+        kinds = tuple(_eval.TREE_LOSS_FAMILIES) + tuple(_eval.MARGIN_LOSS_KINDS)
+        if self.params.get("structured_loss") not in (None,) + kinds:
+            raise ValueError("params['structured_loss'] must be None or one of %s, got %r"
+                             % (", ".join(repr(k) for k in kinds), self.params["structured_loss"]))
+        try:
+            _eval.margin_cost(self.params.get("structured_loss_margin", 1.0))
+        except ValueError:
+            raise ValueError("params['structured_loss_margin'] must be a number in 0..%g, got %r"
+                             % (_eval.MARGIN_COST_MAX, self.params["structured_loss_margin"])) from None
         if self.params.get("structured_loss_single_root", True) not in (True, False):
             raise ValueError("params['structured_loss_single_root'] must be True or False, got %r"
                              % (self.params["structured_loss_single_root"],))
@@ -205,9 +216,12 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
             "hip_graphs": True,           # not in the reference: captured steps for edge-list feeds (graphs.py)
             "hip_graph_cache_mb": 16384,  # not in the reference: device memory the captured steps may hold
             # not in the reference: the head's loss as the negative log-likelihood of the gold TREE
-            # (None: the per-word cross-entropy; "nonprojective" / "projective": ggnn_tree_loss)
+            # (None: the per-word cross-entropy; "nonprojective" / "projective": ggnn_tree_loss;
+            # "nonprojective-margin" / "projective-margin": the structured hinge, ggnn_margin_loss,
+            # with structured_loss_margin the cost of a wrong head)
             "structured_loss": None,
             "structured_loss_single_root": True,
+            "structured_loss_margin": 1.0,
         }
 
     @property
@@ -452,6 +466,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         loss, probs, probs_e = HeadsFunction.apply(oh, labels, keep, seed, target_num, tree_loss, hT, h0,
                                                    gw, gb, gew, geb)
         self.ops["tree_loss_used"] = oh.tree_used
+        self.ops["margin_loss_hamming"] = oh.margin_hamming
         self.ops["loss"] = loss
         self.ops["computed_values"] = probs.reshape(b, v * o)
         self.ops["computed_values_edges"] = probs_e.reshape(b, v * oe)
@@ -477,11 +492,16 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         return float(tmask[self.params["task_ids"].index(task_id)].sum())
 
     def _structured(self):
-        """params['structured_loss'] as (family, single_root) of ggnn_tree_loss, or None (off)."""
+        """params['structured_loss'] as (family, single_root) of ggnn_tree_loss,
+        as (family, single_root, cost) of ggnn_margin_loss, or None (off)."""
         kind = self.params.get("structured_loss")
         if kind is None:
             return None
-        return _eval.TREE_LOSS_FAMILIES[kind], bool(self.params.get("structured_loss_single_root", True))
+        single_root = bool(self.params.get("structured_loss_single_root", True))
+        if kind in _eval.MARGIN_LOSS_KINDS:
+            return (_eval.MARGIN_LOSS_KINDS[kind], single_root,
+                    _eval.margin_cost(self.params.get("structured_loss_margin", 1.0)))
+        return _eval.TREE_LOSS_FAMILIES[kind], single_root
 
     def _loss_n_nodes(self, ph):
         """The node counts the structured loss runs on: _feed_n_nodes, and 0 for
@@ -495,7 +515,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
     def _tree_loss_arg(self, n_nodes):
         """OutputHeads.forward's tree_loss= for device node counts (None: off)."""
         st = self._structured()
-        return None if st is None or n_nodes is None else st + (n_nodes,)
+        return None if st is None or n_nodes is None else st[:2] + (n_nodes,) + st[2:]
 
     def _out_keep(self) -> float:
         return float(self.placeholders.get("out_layer_dropout_keep_prob", self.params["out_layer_dropout_keep_prob"]))
@@ -722,7 +742,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
             else:
                 _, _, probs, loss = self._forward(sf, task_id, training=False)
                 loss = loss.sum()
-            return {"loss": loss, "probs": probs, "used": cs.heads.tree_used}
+            return {"loss": loss, "probs": probs, "used": cs.heads.tree_used, "hamming": cs.heads.margin_hamming}
 
         if cs.graph is None and cs.runs == 0:
             # a shape's first batch runs eagerly (on the same device inputs):
@@ -756,6 +776,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
         self.ops["computed_values"] = probs[0].reshape(b, v * o)
         self.ops["computed_values_edges"] = probs[1].reshape(b, v * oe)
         self.ops["tree_loss_used"] = out["used"]
+        self.ops["margin_loss_hamming"] = out["hamming"]
         self._last_labels = [inp.yh, inp.ye]
         loss = out["loss"]
         if training and not adam:
@@ -810,6 +831,7 @@ class DenseGGNNChemModel(DecodingMixin, BtbBatching):
                                        sf.target_num, loss_out=loss_out, seed_device=sf.seed_device,
                                        tree_loss=self._tree_loss_arg(sf.n_nodes))
         self.ops["tree_loss_used"] = sf.heads.tree_used
+        self.ops["margin_loss_hamming"] = sf.heads.margin_hamming
         self.last_heads = dict(keep=keep_o, seed=sf.seed_values[2], target_num=sf.target_num_value)
         return h0, hT, probs, loss
 

@@ -672,6 +672,70 @@ int ggnn_tree_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, c
                        float* marg, float* logz, int32_t* status, int32_t* used, float* loss_inout,
                        void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
 
+/* The max-margin training loss: the structured hinge over cost-augmented
+ * decoding (Taskar et al. 2004; MSTParser; Kiperwasser & Goldberg 2016), the
+ * max-product twin of ggnn_tree_loss.  For one graph, with s the integer scores
+ * rint(log2 p * 2^k) of the head probabilities (floor -150 * 2^k, k the largest
+ * k <= 16 with 150 * 2^k * v * (v + 1) <= 2^30, GGNN_TREE_FORBIDDEN where the
+ * arc is not allowed), y the gold heads and C = rint(cost * 2^k / ln 2),
+ *   T* = the maximum tree of s'[d][j] = s[d][j] + C [j != y_d] in the family
+ *        (ggnn_tree_decode, family 0; ggnn_projective_decode, family 1),
+ *   l  = sum over the words with T*_d != y_d of ln p[d][T*_d] - ln p[d][y_d] + cost
+ *        (in double, from the float32 p),
+ *   L  = max(0, l),   dL/dz[d][k] = onehot(T*)[d][k] - y[d][k] where l > 0, else 0
+ * (z the head logits: every tree has one head per word, so the rows' logsumexp
+ * cancels between two trees).  l falls short of the true maximum over the
+ * family by at most 1.5 (n - 1) ln 2 * 2^-k, the resolution of the scores.
+ * Eligibility is ggnn_tree_loss's.  A graph is USED when it is eligible and the
+ * decoder's status is 1; for a used graph L replaces the cross-entropy that
+ * ggnn_heads_forward has put into the loss, any other graph keeps it.  The call
+ * runs after ggnn_heads_forward on the same stream and leaves in marg what
+ * ggnn_heads_backward takes in head 0's `probs` place:
+ *   used, l > 0:   onehot(T*) on the rows 1..n-1, zeros elsewhere;
+ *   used, l <= 0:  a copy of gold_head[g] (dZ = 0);
+ *   not used:      a byte copy of probs_head[g].
+ * heads[g][i] = T*_i for the words of a used graph, -1 on node 0, the padding
+ * and every other graph; value[g] = L (0 where not used); hamming[g] = the
+ * number of words with T*_d != y_d (0 where not used); status[g] = the
+ * decoder's (0 for a graph that is not eligible); used[g] = 0 / 1; and
+ *   loss_inout[0] += (sum over the used graphs of L + sum_d ln p[d][y_d]) / target_num,
+ * the per-graph values and the sum in double in a fixed order.  Five launches:
+ * the eligibility kernel of ggnn_tree_loss, the scores, the family's decoder
+ * unchanged (every head of its pred at -1, so it always solves), the per-graph
+ * fold, the sum.  Needs 0 <= cost <= 64 (finite; then |s'| <= 150 * 2^k, the
+ * range the shift guarantees), v <= o, v <= GGNN_TREE_MAXV, o <= 1024; marg
+ * must not alias probs_head.  ggnn_margin_loss_workspace_bytes(b, v, o,
+ * family): n_eff, the per-graph doubles, the gold heads, pred and s' (each
+ * rounded up to 256 bytes) + the decoder's workspace; a smaller workspace is
+ * rejected.  target_num: as ggnn_tree_loss (the _dev form gives the same
+ * bits).  No atomics, no host synchronisation, no allocation; stream-ordered,
+ * legal under stream capture, bit-reproducible; booked under the heads kernel
+ * kind. */
+size_t ggnn_margin_loss_workspace_bytes(int32_t b, int32_t v, int32_t o, int32_t family);
+int ggnn_margin_loss(const ggnn_dims* d,        /* b, v used */
+                     const float* probs_head,   /* device [b][v][o] */
+                     int32_t o,
+                     const float* gold_head,    /* device [b][v][o] */
+                     const int32_t* n_nodes,    /* device [b] */
+                     int32_t family,            /* 0 all dependency trees, 1 projective */
+                     int32_t single_root,       /* 0 / 1 */
+                     float cost,                /* the margin per wrong head, 0..64 */
+                     float target_num,
+                     float* marg,               /* device [b][v][o] out */
+                     int32_t* heads,            /* device [b][v] out */
+                     float* value,              /* device [b] out */
+                     int32_t* hamming,          /* device [b] out */
+                     int32_t* status,           /* device [b] out */
+                     int32_t* used,             /* device [b] out */
+                     float* loss_inout,         /* device float, added to */
+                     void* workspace, size_t workspace_bytes, ggnn_stream_t stream);
+int ggnn_margin_loss_dev(const ggnn_dims* d, const float* probs_head, int32_t o, const float* gold_head,
+                         const int32_t* n_nodes, int32_t family, int32_t single_root, float cost,
+                         const float* target_num, /* device float */
+                         float* marg, int32_t* heads, float* value, int32_t* hamming, int32_t* status,
+                         int32_t* used, float* loss_inout, void* workspace, size_t workspace_bytes,
+                         ggnn_stream_t stream);
+
 /* Dependency trees drawn from the distribution that ggnn_tree_marginals
  * describes (weight of a tree: the product of its words' head probabilities,
  * crossing arcs included; single_root: exactly one ROOT child): num_samples = K

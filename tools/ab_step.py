@@ -19,6 +19,11 @@ otherwise; multi-root, the random trees have several ROOT children;
 projective: a random projective tree of the graph's size, the random trees
 cross): what params['structured_loss'] adds to a step, all three alternating
 in one process.  A first line says how many graphs the loss used.
+
+--structured-loss {nonprojective-margin,projective-margin} (--margin, default
+1.0): every variant runs three times per round: as it is, (name +
+"+tree_loss") with the likelihood loss of the same family (the yardstick) and
+(name + "+margin_loss") with ggnn_margin_loss there, on the same inputs.
 """
 import argparse
 import json
@@ -42,9 +47,15 @@ def main():
     ap.add_argument("--reference", action="store_true",
                     help="with --trees: the reference's model (hidden 400, T = 4), edge lists staged once, pair mode")
     ap.add_argument("--batch", type=int, default=256, help="graphs per batch (20: run_epoch's batch_size)")
-    ap.add_argument("--structured-loss", choices=("nonprojective", "projective"), default=None,
-                    help="also time every variant with ggnn_tree_loss of this family in the step")
+    ap.add_argument("--structured-loss", default=None,
+                    choices=("nonprojective", "projective", "nonprojective-margin", "projective-margin"),
+                    help="also time every variant with ggnn_tree_loss / ggnn_margin_loss of this family in the step")
+    ap.add_argument("--margin", type=float, default=1.0, help="the margin kinds' cost of a wrong head")
     args = ap.parse_args()
+    kind = args.structured_loss
+    margin = bool(kind) and kind.endswith("-margin")
+    if margin:
+        args.structured_loss = kind[:-len("-margin")]      # the family, as the likelihood loss names it
     import torch
     from ggnn_amd import _lib
     from ggnn_amd.dist import GRAD_ORDER, FlatGradients
@@ -135,6 +146,9 @@ def main():
             opt.step([grads.views[k] for k in GRAD_ORDER])
             if extra == "tree_loss":
                 tl["oh"].tree_loss(tl["p"], tl["y"], tl["n"], args.structured_loss, False, tl["tn"], tl["loss"])
+            elif extra == "margin_loss":
+                tl["oh"].margin_loss(tl["p"], tl["y"], tl["n"], args.structured_loss, False, tl["tn"], tl["loss"],
+                                     args.margin)
             elif extra == "marginals":      # the family's marginal kernel alone: the yardstick of the two new launches
                 run = tl["oh"].projective_marginals if args.structured_loss == "projective" else tl["oh"].tree_marginals
                 run(tl["p"], tl["n"], False, with_scores=False)
@@ -143,13 +157,22 @@ def main():
     steps = {}
     for vn in args.variants.split(","):
         steps[vn] = make(vn)
-        if tl is not None:
+        if tl is not None and not margin:
             steps[vn + "+marginals"] = make(vn, "marginals")
+        if tl is not None:
             steps[vn + "+tree_loss"] = make(vn, "tree_loss")
+        if margin:
+            steps[vn + "+margin_loss"] = make(vn, "margin_loss")
     if tl is not None:
         used = tl["oh"].tree_loss(tl["p"], tl["y"], tl["n"], args.structured_loss, False, tl["tn"], tl["loss"])[3]
-        print(json.dumps({"structured_loss": args.structured_loss, "b": b, "v": v, "o": 150,
-                          "used_graphs": int(used.sum().item())}), flush=True)
+        first = {"structured_loss": kind, "b": b, "v": v, "o": 150, "used_graphs": int(used.sum().item())}
+        if margin:
+            out = tl["oh"].margin_loss(tl["p"], tl["y"], tl["n"], args.structured_loss, False, tl["tn"], tl["loss"],
+                                       args.margin)
+            first.update(margin=args.margin, margin_used_graphs=int(out[5].sum().item()),
+                         margin_active_graphs=int((out[2] > 0).sum().item()),
+                         margin_hamming=int(out[3].sum().item()))
+        print(json.dumps(first), flush=True)
     for r in range(args.rounds):
         for vn, step in steps.items():
             for _ in range(10):
